@@ -11,10 +11,20 @@ Philox inside the step, dropout masks drawn on device), reference init N(0,0.005
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  The default run (no --workload) times the headline workload (configs[1], 32x32) and then, in the
-same process and the same JSON line, BASELINE configs[3] / [4] (c2f 64x64: B = 128, D_it = 1 on one GPU; 64 per GPU with D_it = 2 when
-N > 1) as the sub-record "c2f" with its own value / ms_per_step / roofline / step_roofline / cpu_baseline.  N > 1: weak scaling (B=128 per GPU; --strong: B=128 globally), RCCL all-reduce (sum)
-of the flat D / G gradient vectors each update through the library's own communicator (fg_comm_*), replicas identical.
+Prints ONE JSON line on rank 0.  A plain run times the headline workload (configs[1], 32x32) and nothing else: set-up, --warmup
+steps, --steps timed steps, the outputs of the last timed step (--dump-outputs DIR), the line.  With --full the same run goes on, in
+the same process and the same JSON line, with everything else the benchmark measures: the roofline / clock / PMC-traffic legs, the
+supplementary bf16x6 timing, the CPU baselines, host-fed inputs, and BASELINE configs[3] / [4] (c2f 64x64: B = 128, D_it = 1 on one
+GPU; 64 per GPU with D_it = 2 when N > 1) as the sub-record "c2f" with its own value / ms_per_step / roofline / step_roofline /
+cpu_baseline; N > 1 adds the CPU walk of the collective schedule and the multi_gpu legs.  N > 1: weak scaling (B=128 per GPU;
+--strong: B=128 globally), RCCL all-reduce (sum) of the flat D / G gradient vectors each update through the library's own
+communicator (fg_comm_*), replicas identical.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the step receives it, to DIR/<name>.npy (float32; integer
+counts as float64): D_* = the D closure's results (loss, D outputs, confusion counts, the noise and dropout masks drawn on the device),
+G_* = the G closure's (loss, D outputs, generated samples NHWC, noise, masks), params_G / params_D = the flat parameter vectors after
+the step's updates.  Inputs are seeded, so two runs with the same arguments see the same data; at most 64 MB in all (a larger array
+is replaced by a fixed, seeded sample of its elements).
 
 Roofline keys (dominant kernel, HIP events on the launch stream, live in this run):
   roofline.achieved / frac      EXECUTED MFMA TFLOP/s of that kernel and its fraction of the fp32 MFMA peak (<= 1)
@@ -231,6 +241,50 @@ def dominant_launch_clock(ctx, torch, spec, cover_ms=40.0):
         return None, None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def kept(res, prefix):
+    """Copies of the tensors a closure returned (its results are views into workspaces the next closure reuses)."""
+    out = {}
+    for k, v in res.items():
+        if hasattr(v, "clone"):
+            out[prefix + k] = v.clone()
+        elif isinstance(v, list) and v and all(hasattr(t, "clone") for t in v):
+            for i, t in enumerate(v):
+                out["%s%s%d" % (prefix, k, i)] = t.clone()
+    return out
+
+
+def write_outputs(directory, arrays, seed=0):
+    """arrays: name -> tensor.  Writes directory/<name>.npy in float32 (float64 for float64 and integer data); if the whole set
+    exceeds DUMP_LIMIT_BYTES the largest arrays are cut to a common element budget by a fixed, seeded sample (sorted indices into
+    the flattened array).  -> a short summary for the JSON line."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float32 if a.dtype in (np.float32, np.float16) else np.float64)
+    # water-filling: small arrays are kept whole, the rest share what is left of the budget equally
+    budget, left, cap = DUMP_LIMIT_BYTES, len(host), {}
+    for name in sorted(host, key=lambda n: host[n].nbytes):
+        share = budget // left
+        a = host[name]
+        cap[name] = a.size if a.nbytes <= share else share // a.itemsize
+        budget -= cap[name] * a.itemsize
+        left -= 1
+    os.makedirs(directory, exist_ok=True)
+    sampled, total = [], 0
+    for name, a in sorted(host.items()):
+        if cap[name] < a.size:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, cap[name], replace=False))
+            a = a.reshape(-1)[idx]
+            sampled.append(name)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        total += a.nbytes
+    return {"dir": os.path.abspath(directory), "arrays": len(host), "bytes": total, "sampled": sampled}
+
+
 STAGE = {"name": "start", "t0": time.time()}
 
 
@@ -239,8 +293,10 @@ def stage(name):
     STAGE["name"], STAGE["t0"] = name, time.time()
 
 
-def measure(args, ctx, tr, iteration, torch, dist, world, rank, B, flops_per_iter, out, workload, steps, warmup, alt_math=True):
-    """Timed region + roofline leg shared by both workloads.  Fills `out` in place."""
+def measure(args, ctx, tr, iteration, torch, dist, world, rank, B, flops_per_iter, out, workload, steps, warmup, alt_math=True,
+            dump=None):
+    """Timed region (+ with --full the roofline / baseline legs) shared by both workloads.  Fills `out` in place.
+    dump(results): called on every rank right after the timed region with what the last timed step returned."""
     def sync_all():
         torch.cuda.synchronize()
         if world > 1:
@@ -261,8 +317,9 @@ def measure(args, ctx, tr, iteration, torch, dist, world, rank, B, flops_per_ite
     sync_all()
     stage(workload + ": timed steps")
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1 if dump else steps):
         iteration()
+    last = iteration(keep=True) if dump else None
     tr.finish_pending()          # N > 1: the last D update is deferred behind the next G forward -- complete it in-region
     torch.cuda.synchronize()
     dt_local = time.perf_counter() - t0          # this rank's own clock, before the closing barrier: a straggler shows here
@@ -270,6 +327,10 @@ def measure(args, ctx, tr, iteration, torch, dist, world, rank, B, flops_per_ite
     dt = max_over_ranks(time.perf_counter() - t0)
     ms = 1000.0 * dt / steps
     out.update(value=world * B * steps / dt, ms_per_step=ms)
+    if dump:
+        dump(last)
+    if not args.full:
+        return
     if world > 1:
         t = torch.zeros(world, dtype=torch.float64, device=ctx.device)
         t[rank] = 1000.0 * dt_local / steps
@@ -548,13 +609,19 @@ def build_cfg2(args, ctx, torch, coll, world, rank, B):
     tr = adversarial.Trainer(ctx, G, D, S.OPT, dist=coll)
     real = ctx.uniform((B // 2, 32, 32, C), 0.0, 1.0, seed=77 + rank)
 
-    def iteration():
+    def iteration(keep=False):
+        """keep: return copies of what both closures returned (--dump-outputs; the last timed step only)."""
         if tr.gan is not None:        # one C call per closure (fg_step_D / fg_step_G); noise + masks drawn inside it
-            tr.step_D(real, None)
-            tr.step_G(B)
+            rd = tr.step_D(real, None)
+            rd = kept(rd, "D_") if keep else None
+            rg = tr.step_G(B)
         else:
-            tr.step_D(real, S.next_noise(ctx, B // 2, 100))
-            tr.step_G(S.next_noise(ctx, B, 100))
+            rd = tr.step_D(real, S.next_noise(ctx, B // 2, 100))
+            rd = kept(rd, "D_") if keep else None
+            rg = tr.step_G(S.next_noise(ctx, B, 100))
+        if keep:
+            rd.update(kept(rg, "G_"))
+            return rd
     return dict(tr=tr, iteration=iteration, flops=alg_flops_per_iter(B), real=real,
                 data="synthetic (U[0,1) images, U(-1,1) noise, reference init N(0,.005^2)/N(0,.001^2))",
                 config={"workload": "configs[1]: 32x32 color, noiseDim=100, batch %d per GPU, Adam, D_it=G_it=1" % B
@@ -581,16 +648,21 @@ def build_c2f(args, ctx, torch, coll, world, rank, B, d_it):
     h = B // 2
     diff_r, coarse_r, coarse_f = diff[:h].contiguous(), coarse[:h].contiguous(), coarse[h:].contiguous()
 
-    def iteration():
-        for _ in range(d_it):             # adversarial_c2f.lua:123-160: D_iterations closures per G closure
+    def iteration(keep=False):
+        """keep: return copies of what the last D closure and the G closure returned (--dump-outputs; the last timed step only)."""
+        for k in range(d_it):             # adversarial_c2f.lua:123-160: D_iterations closures per G closure
             if tr.gan is not None:        # one C call per closure; noise planes and dropout masks drawn inside it
-                tr.step_D(diff_r, coarse_r, None, coarse_f)
+                rd = tr.step_D(diff_r, coarse_r, None, coarse_f)
             else:
-                tr.step_D(diff_r, coarse_r, S.next_noise(ctx, h, Sz * Sz).view(h, Sz, Sz, 1), coarse_f)
+                rd = tr.step_D(diff_r, coarse_r, S.next_noise(ctx, h, Sz * Sz).view(h, Sz, Sz, 1), coarse_f)
+            rd = kept(rd, "D_") if keep and k == d_it - 1 else None
         if tr.gan is not None:
-            tr.step_G(None, coarse)
+            rg = tr.step_G(None, coarse)
         else:
-            tr.step_G(S.next_noise(ctx, B, Sz * Sz).view(B, Sz, Sz, 1), coarse)
+            rg = tr.step_G(S.next_noise(ctx, B, Sz * Sz).view(B, Sz, Sz, 1), coarse)
+        if keep:
+            rd.update(kept(rg, "G_"))
+            return rd
     which = "configs[3]" if (world == 1 and d_it == 1) else "configs[4]-style"
     return dict(tr=tr, iteration=iteration, flops=(C2F_FLOP_PER_IMAGE if d_it == 1 else C2F_D2_FLOP_PER_IMAGE) * B,
                 data="synthetic (U[0,1) fine images, coarse = image.scale down to 32 and back up to 64 (fg_c2f_coarse_diff), diff = fine - coarse, U(-1,1) noise planes)",
@@ -679,6 +751,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=128, help="per-GPU batch (OPT.batchSize); with --strong the GLOBAL batch")
     ap.add_argument("--strong", action="store_true", help="strong scaling: --batch is the global batch, split over the ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures (roofline / clock / PMC-traffic legs, bf16x6, CPU "
+                         "baselines, host-fed inputs, the c2f sub-record; N > 1: the collective-schedule walk and the multi_gpu legs); "
+                         "the --no-* switches below thin it out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--prof-iters", type=int, default=3)
@@ -691,9 +769,9 @@ def main():
     ap.add_argument("--collective", choices=["auto", "fg_comm", "torch"], default="auto",
                     help="N > 1: gradient all-reduce through the library's own RCCL communicator (fg_comm_*, default) or "
                          "torch.distributed; auto = fg_comm, falling back (and saying so) if its self-test fails")
-    ap.add_argument("--workload", choices=["both", "cfg2", "c2f"], default="both",
-                    help="both (default): the headline cfg2 line plus the c2f sub-record; cfg2: 32x32 G32+D32b only (BASELINE "
-                         "configs[1]); c2f: 64x64 coarse-to-fine (configs[3]) as the line itself")
+    ap.add_argument("--workload", choices=["both", "cfg2", "c2f"], default=None,
+                    help="both (default with --full): the headline cfg2 line plus the c2f sub-record; cfg2 (default without --full): "
+                         "32x32 G32+D32b only (BASELINE configs[1]); c2f: 64x64 coarse-to-fine (configs[3]) as the line itself")
     ap.add_argument("--c2f-steps", type=int, default=10, help="timed steps of the c2f sub-record (3 warm-up steps)")
     ap.add_argument("--c2f-timeout", type=float, default=240.0,
                     help="N > 1: if the c2f sub-record has not finished after this many seconds, rank 0 prints the line without it")
@@ -712,6 +790,8 @@ def main():
                     help="no GPU needed: walk the gradient-exchange path of a --gpus N job for every rank with planning-only contexts "
                          "and print the collective schedule (order, dtype, count, stream) every rank would issue; exit 3 on a mismatch")
     args = ap.parse_args()
+    if args.workload is None:
+        args.workload = "both" if args.full else "cfg2"
     if args.dry_collective:
         return dry_collective(args)
 
@@ -756,7 +836,7 @@ def main():
         watchdog = threading.Timer(args.watchdog, bark)
         watchdog.daemon = True
         watchdog.start()
-        if rank == 0 and not args.no_dry_check:
+        if rank == 0 and args.full and not args.no_dry_check:
             # the one thing that can hang an N-GPU run -- ranks issuing different collectives -- checked first, without a GPU:
             # every rank's fg_step_D / fg_step_G walked by planning-only contexts in a CPU subprocess
             stage("dry collective schedule (CPU)")
@@ -808,7 +888,8 @@ def main():
         "dtype": "f32" if args.math == "f32" else "f32 (emulated: 6 exact bf16 split-plane products, fp32 accumulate)",
     })
     if world > 1:
-        out["dry_collective"] = dry
+        if args.full:
+            out["dry_collective"] = dry
         out["collective"] = coll.describe()
         # loud, top-level: the gradient exchange is NOT the library's own communicator (Trainer then drives the closures from
         # the host instead of fg_step_D / fg_step_G -- config.step_entry says so too)
@@ -823,8 +904,14 @@ def main():
     out["data"] = w["data"]
     out["config"] = w["config"]
     out["config"]["step_entry"] = step_entry(tr)
-    measure(args, ctx, tr, w["iteration"], torch, dist, world, rank, B, w["flops"], out, headline, args.steps, args.warmup)
-    if headline == "cfg2" and world == 1:
+    dump = None
+    if args.dump_outputs:
+        def dump(last):
+            last.update(params_G=tr.dnG.params, params_D=tr.dnD.params)
+            if rank == 0:
+                out["dumped_outputs"] = write_outputs(args.dump_outputs, last)
+    measure(args, ctx, tr, w["iteration"], torch, dist, world, rank, B, w["flops"], out, headline, args.steps, args.warmup, dump=dump)
+    if headline == "cfg2" and world == 1 and args.full:
         # the reference's boundary hands over HOST tensors (dataset[i]:clone() into a FloatTensor, adversarial.lua:244-249):
         # the same K steps with the real half coming from host memory every iteration (NCHW FloatTensor -> H2D -> NHWC);
         # never `value` -- the PCIe-inclusive rate of the contract
@@ -840,7 +927,7 @@ def main():
     out["reference_accounting_images_per_sec"] = out["value"] / 2   # adversarial.lua:305 counts B/2 per iteration
     if watchdog is not None:
         watchdog.cancel()          # the headline is measured; the supplementary legs have their own timers below
-    if world > 1 and headline == "cfg2" and not args.no_multi_gpu_extras:
+    if world > 1 and headline == "cfg2" and args.full and not args.no_multi_gpu_extras:
         import threading
         ex_done = threading.Event()
 
@@ -887,7 +974,7 @@ def main():
             sub["config"]["step_entry"] = step_entry(cw["tr"])
             measure(args, ctx, cw["tr"], cw["iteration"], torch, dist, world, rank, cB, cw["flops"], sub, "c2f", args.c2f_steps, 3,
                     alt_math=False)
-            if world > 1 and not args.no_multi_gpu_extras:
+            if world > 1 and args.full and not args.no_multi_gpu_extras:
                 del cw
                 torch.cuda.empty_cache()
                 stage("c2f: compute-only leg")

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-end evidence on the GPU box: the default bench line (cfg2 + the c2f sub-record, live PMC traffic), kernel traces of both
+# Round-end evidence on the GPU box: the full bench line (cfg2 + the c2f sub-record, live PMC traffic), kernel traces of both
 # workloads, PMC passes on the dominant kernels.  usage (through gpurun): bash scripts/collect_profiles.sh <tag>
 #   -> gpurun_out/<tag>_*; copy what is to be judged into profiles/
 set -u
@@ -7,11 +7,11 @@ TAG=${1:-r05}
 OUT=gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p $OUT
-python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
-python bench.py --workload c2f --steps 10 --warmup 3 > $OUT/${TAG}_bench_c2f.json 2> $OUT/${TAG}_bench_c2f.err
-rocprofv3 --kernel-trace --stats -d $OUT/p1 -o run -- python bench.py --workload cfg2 --steps 50 --warmup 10 --no-cpu-baseline --no-alt-math --no-roofline > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
+python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python bench.py --full --workload c2f --steps 10 --warmup 3 > $OUT/${TAG}_bench_c2f.json 2> $OUT/${TAG}_bench_c2f.err
+rocprofv3 --kernel-trace --stats -d $OUT/p1 -o run -- python bench.py --full --workload cfg2 --steps 50 --warmup 10 --no-cpu-baseline --no-alt-math --no-roofline > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
 python scripts/rocpd_stats.py $OUT/p1/run_results.db auto --by-grid > $OUT/${TAG}_bench_kernel_stats.md
-rocprofv3 --kernel-trace --stats -d $OUT/p2 -o run -- python bench.py --workload c2f --steps 6 --warmup 2 --no-cpu-baseline --no-alt-math --no-roofline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/p2 -o run -- python bench.py --full --workload c2f --steps 6 --warmup 2 --no-cpu-baseline --no-alt-math --no-roofline > /dev/null 2>&1
 python scripts/rocpd_stats.py $OUT/p2/run_results.db auto > $OUT/${TAG}_c2f_kernel_stats.md
 rm -f $OUT/${TAG}_pmc_raw.txt
 for which in fwd wgrad; do

@@ -43,9 +43,9 @@ conv)
   cat $OUT/${TAG}_cfg2.txt $OUT/${TAG}_c2f.txt ;;
 kstats)
   TAG=${1:-ks}
-  rocprofv3 --kernel-trace --stats -d $OUT/p1 -o run -- python bench.py --workload cfg2 --steps 50 --warmup 10 --no-cpu-baseline --no-alt-math --no-roofline > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
+  rocprofv3 --kernel-trace --stats -d $OUT/p1 -o run -- python bench.py --full --workload cfg2 --steps 50 --warmup 10 --no-cpu-baseline --no-alt-math --no-roofline > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
   python scripts/rocpd_stats.py $OUT/p1/run_results.db auto --by-grid > $OUT/${TAG}_bench_kernel_stats.md
-  rocprofv3 --kernel-trace --stats -d $OUT/p2 -o run -- python bench.py --workload c2f --steps 6 --warmup 2 --no-cpu-baseline --no-alt-math --no-roofline > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats -d $OUT/p2 -o run -- python bench.py --full --workload c2f --steps 6 --warmup 2 --no-cpu-baseline --no-alt-math --no-roofline > /dev/null 2>&1
   python scripts/rocpd_stats.py $OUT/p2/run_results.db auto > $OUT/${TAG}_c2f_kernel_stats.md
   rm -rf $OUT/p1 $OUT/p2
   head -45 $OUT/${TAG}_bench_kernel_stats.md; head -40 $OUT/${TAG}_c2f_kernel_stats.md ;;
@@ -79,7 +79,7 @@ pmc-tail)
   rm -f $OUT/${TAG}.txt
   for pmc in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU GRBM_GUI_ACTIVE" "TCC_HIT_sum TCC_MISS_sum" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_SALU SQ_BUSY_CYCLES"; do
     d=$OUT/pmc_$(echo $pmc | tr ' ' '_' | cut -c1-40)
-    timeout 300 rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $d -- python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-alt-math --no-roofline > /dev/null 2>&1
+    timeout 300 rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $d -- python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-alt-math --no-roofline > /dev/null 2>&1
     echo "## $pmc" >> $OUT/${TAG}.txt
     for k in pack_jobs wgrad_finish_jobs actpool_bwd actpool_fwd adam_kernel bn_apply; do python scripts/pmc_summary.py $d $k >> $OUT/${TAG}.txt 2>&1; done
     rm -rf $d

@@ -65,7 +65,7 @@ def test_trainer_with_rccl_world1_matches_plain_trainer():
 def test_bench_runs_under_torchrun_single_rank():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
-           "--warmup", "1", "--batch", "16", "--no-cpu-baseline", "--no-live-traffic", "--c2f-steps", "2"]
+           "--warmup", "1", "--batch", "16", "--full", "--no-cpu-baseline", "--no-live-traffic", "--c2f-steps", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

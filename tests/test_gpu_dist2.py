@@ -60,7 +60,7 @@ def test_bench_multi_rank_control_flow_on_one_gpu():
     env = dict(os.environ, FG_BENCH_TEST_GLOO="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29583", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--batch", "16", "--c2f-steps", "1"]
+           "--batch", "16", "--full", "--c2f-steps", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -101,7 +101,7 @@ def test_bench_watchdog_prints_a_partial_line_naming_the_stage():
     env = dict(os.environ, FG_BENCH_TEST_GLOO="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29587", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--batch", "16", "--c2f-steps", "1", "--watchdog", "0.3", "--no-dry-check"]
+           "--batch", "16", "--full", "--c2f-steps", "1", "--watchdog", "0.3", "--no-dry-check"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode != 0
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -3,8 +3,9 @@
   * every `C.fg_*(...)` call names an entry the header declares, with the declared number of arguments;
   * every `C.FG_*` constant is an enumerator of the header;
   * every optimizer path tells the net that its parameters moved (the round-1 shim left the packed weights stale);
-  * the shipped patches apply to the reference's own scripts (checked where /root/reference exists)."""
+  * the shipped patches apply to the reference's own scripts (facts recorded in tests/golden/lua_reference_facts.json)."""
 import glob
+import json
 import os
 import re
 import subprocess
@@ -101,42 +102,100 @@ def test_optimizers_mark_the_packed_weights_stale():
     assert "m.dW == 2" in code and "'nn.SpatialMaxPooling'" in code and "'nn.JoinTable'" in code and "fg_add" in code
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree is only present in the build container")
-def test_patches_apply_to_the_reference_scripts(tmp_path):
+# ---------------------------------------------------------------------------------------------------------------------------
+# The reference's own scripts are not part of this repository: what the two tests below need to know about them -- hashes, whether
+# each patch applies, the free names of every script, the offsets of the probe strings below in the patched scripts -- is recorded
+# in tests/golden/lua_reference_facts.json by tests/golden/make_lua_reference_facts.py, for the patches as they are.  A patch whose
+# sha256 differs from the recorded one fails here until the facts are regenerated.
+# ---------------------------------------------------------------------------------------------------------------------------
+FACTS = os.path.join(ROOT, "tests", "golden", "lua_reference_facts.json")
+CUDA_PROBES = ["re:require\\s+'(cutorch|cunn|cudnn)'", "cutorch.", ":cuda()", "CudaTensor"]
+PATCHED_RELS = ("train.lua", "sample.lua", "utils/nn_utils.lua", "layers/cudnnSpatialConvolutionUpsample.lua", "train_c2f.lua",
+                "models_c2f.lua", "dataset_c2f.lua")
+PATCHED_PROBES = {rel: list(CUDA_PROBES) for rel in PATCHED_RELS}
+PATCHED_PROBES["models_c2f.lua"] += [
+    "FG.attach(model_G:get(3), {dimensions[1]+1, dimensions[2], dimensions[3]}, OPT.batchSize)",
+    "FG.attach(model_D:get(3), {dimensions[1], dimensions[2], dimensions[3]}, OPT.batchSize)",
+    "nn.Copy('torch.FloatTensor', 'torch.FloatTensor')", "nn.JoinTable(2, 2)"]
+PATCHED_PROBES["dataset_c2f.lua"] += [
+    "function dataset._toResult", "local result = {}", "FG.coarseDiff(fineImages, dataset.coarseScale)", "image.scale", "image.load",
+    "result.coarse = coarseImages", "result.diff = diffImages"]
+PATCHED_PROBES["train_c2f.lua"] += [
+    "FG = require 'facegen_hip'", "DATASET.loadImages(0, 500)", "ADVERSARIAL = require 'adversarial_c2f_hip'", "FG.setDevice(OPT.gpu + 1)",
+    "FG.manualSeed(OPT.seed)", "MODELS.create_D(IMG_DIMENSIONS, OPT.gpu ~= false)",
+    "FG.attach(MODEL_G:get(3), {IMG_DIMENSIONS[1] + 1, IMG_DIMENSIONS[2], IMG_DIMENSIONS[3]}, OPT.batchSize)"]
+
+
+class PatchedScript(object):
+    """A patched reference script as the facts record it: the offsets of every probe in its comment-stripped text."""
+    def __init__(self, rel, offsets):
+        self.rel, self.offsets = rel, offsets
+
+    def find_all(self, probe):
+        assert probe in self.offsets, "%s: probe %r not recorded -- run tests/golden/make_lua_reference_facts.py" % (self.rel, probe)
+        return self.offsets[probe]
+
+    def count(self, probe, lo=0, hi=None):
+        n = len(probe)
+        return sum(1 for o in self.find_all(probe) if o >= lo and (hi is None or o + n <= hi))
+
+    def __contains__(self, probe):
+        return self.count(probe) > 0
+
+    def index(self, probe):
+        return self.find_all(probe)[0]
+
+
+def reference_facts():
+    """The recorded facts, after checking they were taken with the patches as they are now."""
+    import hashlib
+    facts = json.load(open(FACTS))
+    patches = sorted(glob.glob(os.path.join(ROOT, "lua", "patches", "*.patch")))
+    assert sorted(facts["patches"]) == [os.path.basename(p) for p in patches], \
+        "lua/patches/ differs from the recorded set -- run tests/golden/make_lua_reference_facts.py"
+    for p in patches:
+        assert hashlib.sha256(open(p, "rb").read()).hexdigest() == facts["patches"][os.path.basename(p)]["sha256"], \
+            "%s changed since the facts were recorded -- run tests/golden/make_lua_reference_facts.py" % os.path.basename(p)
+    return facts
+
+
+def test_patches_apply_to_the_reference_scripts():
+    facts = reference_facts()
     patches = sorted(glob.glob(os.path.join(ROOT, "lua", "patches", "*.patch")))
     assert len(patches) >= 6 and {"train_c2f.lua.patch", "models_c2f.lua.patch"} <= {os.path.basename(p) for p in patches}
+    touched = set()
     for p in patches:
-        r = subprocess.run(["patch", "-p1", "--dry-run", "-d", "/root/reference", "-i", p], capture_output=True, text=True)
-        assert r.returncode == 0, "%s does not apply: %s" % (os.path.basename(p), r.stdout + r.stderr)
+        rec = facts["patches"][os.path.basename(p)]
+        assert rec["applies"], "%s does not apply to the reference" % os.path.basename(p)
+        targets = sorted(set(re.findall(r"^\+\+\+ b/(\S+)", open(p).read(), re.M)))
+        assert targets and targets == rec["targets"], os.path.basename(p)
+        for t in targets:
+            assert t in facts["scripts"], "%s patches %s, which is not a script of the reference" % (os.path.basename(p), t)
+        touched.update(targets)
     # after patching, no CUDA rock is required on the training / sampling path
-    import shutil
-    RELS = ("train.lua", "sample.lua", "utils/nn_utils.lua", "layers/cudnnSpatialConvolutionUpsample.lua", "train_c2f.lua", "models_c2f.lua",
-            "dataset_c2f.lua")
-    for rel in RELS:
-        os.makedirs(os.path.dirname(os.path.join(str(tmp_path), rel)), exist_ok=True)
-        shutil.copy(os.path.join("/root/reference", rel), os.path.join(str(tmp_path), rel))
-    for p in patches:
-        subprocess.run(["patch", "-p1", "-s", "-d", str(tmp_path), "-i", p], check=True)
-    for rel in RELS:
-        code = strip_lua_comments(open(os.path.join(str(tmp_path), rel)).read())
-        assert not re.search(r"require\s+'(cutorch|cunn|cudnn)'", code), "%s still requires a CUDA rock" % rel
-        assert "cutorch." not in code and ":cuda()" not in code, "%s still calls into cutorch" % rel
-        assert "CudaTensor" not in code, "%s still names torch.CudaTensor" % rel
+    assert set(PATCHED_RELS) <= touched
+    assert sorted(facts["probes"]) == sorted(PATCHED_RELS)
+    code = {rel: PatchedScript(rel, facts["probes"][rel]) for rel in PATCHED_RELS}
+    for rel in PATCHED_RELS:
+        c = code[rel]
+        assert not c.count("re:require\\s+'(cutorch|cunn|cudnn)'"), "%s still requires a CUDA rock" % rel
+        assert "cutorch." not in c and ":cuda()" not in c, "%s still calls into cutorch" % rel
+        assert "CudaTensor" not in c, "%s still names torch.CudaTensor" % rel
     # configs 4-5 (VERDICT r3 item 2): every create_G_* / create_D_* variant of models_c2f.lua keeps its {first, Copy, inner, Copy}
     # shape and hands the inner Sequential to FG.attach with the dimensions its first layer takes; train_c2f.lua binds the library,
     # selects the re-hosted loop and re-attaches a reloaded checkpoint
-    mc = strip_lua_comments(open(os.path.join(str(tmp_path), "models_c2f.lua")).read())
+    mc = code["models_c2f.lua"]
     assert mc.count("FG.attach(model_G:get(3), {dimensions[1]+1, dimensions[2], dimensions[3]}, OPT.batchSize)") == 4
     assert mc.count("FG.attach(model_D:get(3), {dimensions[1], dimensions[2], dimensions[3]}, OPT.batchSize)") == 3
     assert mc.count("nn.Copy('torch.FloatTensor', 'torch.FloatTensor')") == 14 and mc.count("nn.JoinTable(2, 2)") == 4
     # round 6: dataset._toResult (dataset_c2f.lua:49-61) hands image.scale down / up and the subtraction to the library; the `image`
     # package stays required for image.load only, and FG is bound (train_c2f.lua) before DATASET.loadImages runs
-    dc = strip_lua_comments(open(os.path.join(str(tmp_path), "dataset_c2f.lua")).read())
-    body = dc[dc.index("function dataset._toResult"):dc.index("local result = {}")]
-    assert "FG.coarseDiff(fineImages, dataset.coarseScale)" in body and "image.scale" not in body
+    dc = code["dataset_c2f.lua"]
+    lo, hi = dc.index("function dataset._toResult"), dc.index("local result = {}")
+    assert dc.count("FG.coarseDiff(fineImages, dataset.coarseScale)", lo, hi) and not dc.count("image.scale", lo, hi)
     assert dc.count("image.scale") == 2 and "image.load" in dc        # the JPEG loader (dataset_c2f.lua:111-215, out of scope) keeps its own
     assert "result.coarse = coarseImages" in dc and "result.diff = diffImages" in dc
-    tc = strip_lua_comments(open(os.path.join(str(tmp_path), "train_c2f.lua")).read())
+    tc = code["train_c2f.lua"]
     assert tc.index("FG = require 'facegen_hip'") < tc.index("DATASET.loadImages(0, 500)")
     assert "ADVERSARIAL = require 'adversarial_c2f_hip'" in tc and "FG = require 'facegen_hip'" in tc
     assert tc.index("FG = require 'facegen_hip'") < tc.index("FG.setDevice(OPT.gpu + 1)") < tc.index("FG.manualSeed(OPT.seed)") \
@@ -341,37 +400,28 @@ def test_a_broken_end_then_or_comma_is_caught_in_every_file():
                 lua_parse(bad)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree is only present in the build container")
-def test_patched_reference_scripts_parse_and_define_what_the_rehosted_files_read(tmp_path):
-    """Every reference script, untouched and after lua/patches/*.patch, is valid Lua 5.1; and every free name the re-hosted loops
-    read is a Lua / LuaJIT library name, a global the (patched) host script assigns before it calls the loop, or a name the
-    reference's own version of that file reads as well (train.lua:71-94 sets OPT, MODEL_G, NN_UTILS, CONFUSION, ...)."""
-    import shutil
-    ref = "/root/reference"
-    scripts = sorted(glob.glob(os.path.join(ref, "*.lua")) + glob.glob(os.path.join(ref, "*", "*.lua")))
+def test_patched_reference_scripts_parse_and_define_what_the_rehosted_files_read():
+    """Every reference script, untouched and after lua/patches/*.patch, is valid Lua 5.1 (recorded with this parser); and every free
+    name the re-hosted loops read is a Lua / LuaJIT library name, a global the (patched) host script assigns before it calls the loop,
+    or a name the reference's own version of that file reads as well (train.lua:71-94 sets OPT, MODEL_G, NN_UTILS, CONFUSION, ...)."""
+    facts = reference_facts()
+    scripts = facts["scripts"]
     assert len(scripts) >= 15
-    for s in scripts:
-        lua_parse(open(s).read())                                                   # the checker accepts all of upstream's Lua
-        rel = os.path.relpath(s, ref)
-        os.makedirs(os.path.dirname(os.path.join(str(tmp_path), rel)) or str(tmp_path), exist_ok=True)
-        shutil.copy(s, os.path.join(str(tmp_path), rel))
-    for p in sorted(glob.glob(os.path.join(ROOT, "lua", "patches", "*.patch"))):
-        subprocess.run(["patch", "-p1", "-s", "-d", str(tmp_path), "-i", p], check=True)
-    parsed = {}
-    for s in scripts:
-        rel = os.path.relpath(s, ref)
-        parsed[rel] = lua_parse(open(os.path.join(str(tmp_path), rel)).read())      # ... and all of it after the patches
+    for rel, s in sorted(scripts.items()):
+        assert s["parses"], "the checker rejects the reference's %s" % rel                  # the checker accepts all of upstream's Lua
+        assert s["patched_parses"], "%s does not parse after lua/patches/" % rel             # ... and all of it after the patches
     mine = {os.path.basename(p): lua_parse(open(p).read()) for p in LUA}
     binding = mine["facegen_hip.lua"]
     extra = set(binding.globals_read) - LUA_STDLIB - {"torch", "IMG_DIMENSIONS"}
     assert not extra, "lua/facegen_hip.lua reads undefined globals: %s" % sorted(extra)
     for host, loop, upstream in (("train.lua", "adversarial_hip.lua", "adversarial.lua"),
                                  ("train_c2f.lua", "adversarial_c2f_hip.lua", "adversarial_c2f.lua")):
-        defined = set(parsed[host].globals_written) | set(mine[loop].globals_written)
-        theirs = set(lua_parse(open(os.path.join(ref, upstream)).read()).globals_read)
+        host_written = set(scripts[host]["patched_globals_written"])
+        defined = host_written | set(mine[loop].globals_written)
+        theirs = set(scripts[upstream]["globals_read"])
         unknown = set(mine[loop].globals_read) - LUA_STDLIB - defined - theirs
         assert not unknown, "%s reads %s, which %s never assigns and %s never reads" % (loop, sorted(unknown), host, upstream)
         # the patched host still assigns everything the loop reads from it, and binds the library before building the nets
         for name in ("OPT", "MODEL_G", "MODEL_D", "NN_UTILS", "CONFUSION", "OPTSTATE", "EPOCH", "IMG_DIMENSIONS", "ADVERSARIAL"):
-            assert name in parsed[host].globals_written, "%s (patched) no longer assigns %s" % (host, name)
-        assert "FG" in parsed[host].globals_written, "%s (patched) does not bind the library (FG = require 'facegen_hip')" % host
+            assert name in host_written, "%s (patched) no longer assigns %s" % (host, name)
+        assert "FG" in host_written, "%s (patched) does not bind the library (FG = require 'facegen_hip')" % host
