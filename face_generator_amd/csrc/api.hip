@@ -64,7 +64,6 @@ static int g_dry_ctx = 0;
 int fg_ctx_create(int device, fg_ctx** out) {
     if (!out) return fg_set_err(nullptr, FG_ERR_INVALID, "fg_ctx_create: null out");
     if (const char* m = getenv("FG_LAUNCH_LOG")) g_fg_launch_log = atoi(m) != 0;
-    fg_plan_env_init();
     if (device == FG_DEVICE_NONE) {
         if (g_real_ctx) return fg_set_err(nullptr, FG_ERR_INVALID, "fg_ctx_create: a planning-only context cannot join a process that holds a device context");
         fg_ctx* c = new fg_ctx();

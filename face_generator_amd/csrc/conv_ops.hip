@@ -82,41 +82,34 @@ static void choose_igemm(long long M, int Npad, int ksteps, int P, int math, int
     long long b1 = (long long)fg_cdiv(M, 128) * (Npad / 64) * P;
     long long b2 = (long long)fg_cdiv(M, 64) * (Npad / 64) * P;
     *splits = 1;
-    {   // large layers: wave-specialised 256x128 kernel when it fills the chip with whole rounds of 256 blocks
-        static int use_ws = -1;
-        if (use_ws < 0) { const char* e = getenv("FG_IGEMM_WS"); use_ws = e ? atoi(e) : 1; }
-        const long long bw = (Npad % 64 == 0) ? (long long)fg_cdiv(M, 256) * (Npad / ((Npad % 128 == 0) ? 128 : 64)) * P : 0;
-        if (use_ws && bw >= 256 && bw % 256 == 0 && M % 256 == 0) { *tile = 4; return; }
-        // fp32: layers whose 256x128 tiling leaves part of the chip idle but whose 256x64 tiling gives whole rounds of 256
-        // blocks (D's first mid-size convolution, G's first up-convolution at half batch): tile 5 = the same kernel, BN = 64
-        if (use_ws && math != 6 && Npad % 128 == 0 && M % 256 == 0) {
-            const long long bw64 = (long long)(M / 256) * (Npad / 64) * P;
-            if (bw64 >= 256 && bw64 % 256 == 0) { *tile = 5; return; }
-        }
-        // bf16x6: a K-step is short and cheap, so mid-size layers also use the wave-specialised kernel (256x64 tiles for
-        // layers with 64 output channels), split over K so that exactly one round of 256 blocks fills the chip
-        // (>= 12 sixteen-channel steps per block)
-        if (use_ws && math == 6 && Npad % 64 == 0 && M % 256 == 0) {
-            const int bn = (Npad % 128 == 0) ? 128 : 64;
-            const long long b6 = (long long)(M / 256) * (Npad / bn) * P;
-            if (b6 >= 256 && b6 % 256 == 0) { *tile = 4; return; }
-            if (b6 > 0 && b6 < 256 && 256 % b6 == 0 && (2 * ksteps) / (256 / b6) >= 12) { *tile = 4; *splits = (int)(256 / b6); return; }
-        }
+    // large layers: wave-specialised 256x128 kernel when it fills the chip with whole rounds of 256 blocks
+    const long long bw = (Npad % 64 == 0) ? (long long)fg_cdiv(M, 256) * (Npad / ((Npad % 128 == 0) ? 128 : 64)) * P : 0;
+    if (bw >= 256 && bw % 256 == 0 && M % 256 == 0) { *tile = 4; return; }
+    // fp32: layers whose 256x128 tiling leaves part of the chip idle but whose 256x64 tiling gives whole rounds of 256
+    // blocks (D's first mid-size convolution, G's first up-convolution at half batch): tile 5 = the same kernel, BN = 64
+    if (math != 6 && Npad % 128 == 0 && M % 256 == 0) {
+        const long long bw64 = (long long)(M / 256) * (Npad / 64) * P;
+        if (bw64 >= 256 && bw64 % 256 == 0) { *tile = 5; return; }
+    }
+    // bf16x6: a K-step is short and cheap, so mid-size layers also use the wave-specialised kernel (256x64 tiles for
+    // layers with 64 output channels), split over K so that exactly one round of 256 blocks fills the chip
+    // (>= 12 sixteen-channel steps per block)
+    if (math == 6 && Npad % 64 == 0 && M % 256 == 0) {
+        const int bn = (Npad % 128 == 0) ? 128 : 64;
+        const long long b6 = (long long)(M / 256) * (Npad / bn) * P;
+        if (b6 >= 256 && b6 % 256 == 0) { *tile = 4; return; }
+        if (b6 > 0 && b6 < 256 && 256 % b6 == 0 && (2 * ksteps) / (256 / b6) >= 12) { *tile = 4; *splits = (int)(256 / b6); return; }
     }
     if (b0 >= target) { *tile = 0; return; }
     if (b1 >= target) { *tile = 1; return; }
-    {   // a Linear over very many input features and few samples (65536 -> 512 at M = 128, models_c2f.lua:262: 8.6 GFLOP): 128 x 128
-        // tiles split over K until one round of 256 blocks fills the chip, instead of 64 x 64 tiles capped at 16 splits (round 4;
-        // FG_LINEAR_FWD128=0 switches back)
-        static int on = -1;
-        if (on < 0) { const char* e = getenv("FG_LINEAR_FWD128"); on = e ? atoi(e) : 1; }
-        if (on && math != 6 && b0 > 0 && b0 <= 16 && ksteps >= 1024) {
-            int s = (int)(256 / b0);
-            if (s > ksteps / 16) s = ksteps / 16;
-            const int per = (ksteps + s - 1) / s;
-            *tile = 0; *splits = (ksteps + per - 1) / per;
-            return;
-        }
+    // a Linear over very many input features and few samples (65536 -> 512 at M = 128, models_c2f.lua:262: 8.6 GFLOP): 128 x 128
+    // tiles split over K until one round of 256 blocks fills the chip, instead of 64 x 64 tiles capped at 16 splits (round 4)
+    if (math != 6 && b0 > 0 && b0 <= 16 && ksteps >= 1024) {
+        int s = (int)(256 / b0);
+        if (s > ksteps / 16) s = ksteps / 16;
+        const int per = (ksteps + s - 1) / s;
+        *tile = 0; *splits = (ksteps + per - 1) / per;
+        return;
     }
     *tile = 2;
     // (a contraction of <= 4 K-steps over >= 128 tiles -- G's first Linear, 100 -> 8192 -- is shorter than the extra pass that
@@ -129,6 +122,12 @@ static void choose_igemm(long long M, int Npad, int ksteps, int P, int math, int
         s = (ksteps + per - 1) / per;   // every split non-empty
         *splits = s < 1 ? 1 : s;
     }
+}
+// the forward / data-gradient plan of an implicit-GEMM launch: choose_igemm, except that bf16x6 takes the wave-specialised tile
+// only where both operands split into 16-channel planes (A: Ca channels per pixel, B: Kpad per row); elsewhere the fp32 choice
+static void plan_igemm(long long M, int Npad, int ksteps, int P, int math, int Ca, int Kpad, int* tile, int* splits) {
+    choose_igemm(M, Npad, ksteps, P, math, tile, splits);
+    if (*tile == 4 && math == 6 && (Ca % 16 || Kpad % 16)) choose_igemm(M, Npad, ksteps, P, 0, tile, splits);
 }
 static void fill_wino(WinoArgs& w, const ConvGeom& g, int bwd);
 // Winograd launch: blocks of 64 tiles x 64 output channels; when they do not fill the chip the K chunks (8 channels each) are
@@ -149,13 +148,6 @@ static int choose_wino_splits(long long T, int Npad, int C) {      // Npad: all 
 // busy (D's 64 -> 128 ... 256 -> 512 layers on 16x16 ... 4x4 maps do not: 2 ... 32 channel blocks; they keep the tap-by-tap
 // kernels).  false = not taken.
 static long long g_ww_min_chunks = 24, g_ww_min_blocks = 192;
-void fg_plan_env_init() {
-    static bool done = false;
-    if (done) return;
-    done = true;
-    if (const char* e = getenv("FG_WINO_WGRAD_MIN_CHUNKS")) g_ww_min_chunks = atoll(e) > 0 ? atoll(e) : 1;
-    if (const char* e = getenv("FG_WINO_WGRAD_MIN_BLOCKS")) g_ww_min_blocks = atoll(e);
-}
 void fg_plan_set_wino_wgrad_thresholds(long long min_chunks, long long min_blocks) {
     g_ww_min_chunks = min_chunks > 0 ? min_chunks : 24;
     g_ww_min_blocks = min_blocks > 0 ? min_blocks : 192;
@@ -168,8 +160,7 @@ static bool choose_wino_wgrad(const ConvGeom& g, int* S, int* cps) {
     int P, KG; fg_wino_pack_shape(wm.kind, g.wino, 0, &P, &KG);
     const long long T = (long long)g.B * TH * TW, nct = (T + 7) / 8;
     const long long base = (long long)(g.Cout / 64) * (g.Cin / 64) * P * KG;
-    // (planning thresholds of the process: the environment is read once, at the first fg_ctx_create; the parity tests reach the
-    // small-shape corners through fg_test_set_wino_wgrad_thresholds)
+    // (planning thresholds of the process: the parity tests reach the small-shape corners through fg_test_set_wino_wgrad_thresholds)
     const long long min_chunks = g_ww_min_chunks, min_blocks = g_ww_min_blocks;
     long long s = base >= 256 ? 1 : 256 / base;
     if (s > nct / min_chunks) s = nct / min_chunks;
@@ -186,13 +177,9 @@ static long long wino_wgrad_part_floats(const ConvGeom& g, int S) {
 }
 static void choose_wgrad(long long M, int Cout, int Cin, int G, int P, int* tile, int* S, int* mper, int* Npad, int* Cpad) {
     int bt = (Cout >= 128 && Cin >= 128) ? 128 : 64;
-    {   // a Linear layer reduces over the B samples only (M = 128): with 128 x 128 tiles Linear(2048, 512) is 64 blocks of 8 K-steps
-        // on a quarter of the chip, all prologue and epilogue (24 us for 0.27 GFLOP); 64 x 64 tiles give 256 blocks (round 4;
-        // FG_LINEAR_WGRAD64=0 switches back)
-        static int on = -1;
-        if (on < 0) { const char* e = getenv("FG_LINEAR_WGRAD64"); on = e ? atoi(e) : 1; }
-        if (on && G == 1 && P == 1 && M <= 256 && (long long)Cout * Cin <= (1LL << 21)) bt = 64;     // (not the 65536 x 512 layer of models_c2f.lua:262: 8.6 GFLOP)
-    }
+    // a Linear layer reduces over the B samples only (M = 128): with 128 x 128 tiles Linear(2048, 512) is 64 blocks of 8 K-steps
+    // on a quarter of the chip, all prologue and epilogue (24 us for 0.27 GFLOP); 64 x 64 tiles give 256 blocks (round 4)
+    if (G == 1 && P == 1 && M <= 256 && (long long)Cout * Cin <= (1LL << 21)) bt = 64;     // (not the 65536 x 512 layer of models_c2f.lua:262: 8.6 GFLOP)
     *tile = bt == 128 ? 0 : 2;
     *Npad = fg_round_up(Cout, bt);
     *Cpad = fg_round_up(Cin, bt);
@@ -220,11 +207,9 @@ static void choose_wgrad(long long M, int Cout, int Cin, int G, int P, int* tile
 // One block per CU and `base` blocks per pixel split: s splits fill base*s / (256 * rounds) of the chip -- 25 taps x 10 splits = 250
 // blocks leave 6 CUs idle for the whole launch (2.3 % of the 6.8 ms 5x5 weight gradient of models_c2f.lua:122).  When every block
 // would still run >= 512 K-steps, take the number of ROUNDS (<= 6) whose last round is fullest: 25 x 51 = 1275 blocks = 4.98 rounds.
-// More splits are more partial sums to write and add up, so a later round count must win by 1 % (FG_WGRAD_ROUNDS=0: one round).
+// More splits are more partial sums to write and add up, so a later round count must win by 1 %.
 static long long fg_wgrad_rounds(long long base, long long s1, long long M, int kstep) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("FG_WGRAD_ROUNDS"); on = e ? atoi(e) : 1; }
-    if (!on || base <= 0) return s1;
+    if (base <= 0) return s1;
     long long best = s1;
     double beff = (double)(base * s1) / (double)(256 * ((base * s1 + 255) / 256));
     for (int r = 2; r <= 6; ++r) {
@@ -259,13 +244,11 @@ static int choose_wgrad6(long long M, int Cout, int Cin, int G, int P, int* S, i
 }
 
 // fp32 wave-specialised weight gradient: the tilings of choose_wgrad6, else (round 3) 128 dY x 64 X channels with the K-step split
-// over the MFMA waves (cfg 2: the 64 -> 128 layers of models_c2f.lua; 64-pixel K-steps, FG_WGRAD_WS64=0 switches it off)
+// over the MFMA waves (cfg 2: the 64 -> 128 layers of models_c2f.lua; 64-pixel K-steps)
 static int choose_wgrad_ws(long long M, int Cout, int Cin, int G, int P, int* S, int* mper) {
     const int c = choose_wgrad6(M, Cout, Cin, G, P, S, mper);
     if (c >= 0) return c;
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("FG_WGRAD_WS64"); on = e ? atoi(e) : 1; }
-    if (!on || Cout % 128 || Cin % 64) return -1;
+    if (Cout % 128 || Cin % 64) return -1;
     const long long base = (long long)(Cout / 128) * (Cin / 64) * G * P;
     long long s = (256 + base / 2) / base;
     if (base * s > 256 && s > 1 && base * s - 256 < base / 2) s -= 1;
@@ -279,62 +262,100 @@ static int choose_wgrad_ws(long long M, int Cout, int Cin, int G, int P, int* S,
     return 2;
 }
 
-// A/B switch (round 3; default on): FG_WGRAD_WS=0 keeps the symmetric wgrad_kernel for the layers that tile 256 x 128 /
-// 128 x 256 channels instead of the wave-specialised wgrad_ws_kernel
-// smallest pixel count the wave-specialised weight gradient takes (measurement knob: FG_WGRAD_WS_MINM; default 4096)
-static long long fg_wgrad_ws_minm() {
-    static long long v = -1;
-    if (v < 0) { const char* e = getenv("FG_WGRAD_WS_MINM"); v = e ? atoll(e) : 4096; if (v < 256) v = 256; }
-    return v;
-}
-static bool fg_wgrad_ws_on() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("FG_WGRAD_WS"); v = e ? atoi(e) : 1; }
-    return v != 0;
-}
-
-// floats of split-K / parity partials the fp32 weight gradient of this layer leaves (upper bound over its two kernels): what the
-// deferred-finals arena of a net reserves per convolution so that the partials survive until the end of the backward pass
-long long fg_conv_wgrad_part_floats(const ConvGeom& g) {
+// ---- the weight gradient: ONE decision per call (plan_wgrad), taken by the runner and by every sizer ----
+enum { WG_TAPS, WG_WS, WG_BF16X6, WG_WINO };
+static const char* const wg_path_name[4] = {"tap-by-tap", "ws", "bf16x6", "winograd"};
+struct WgradPlan {
+    int path;           // WG_*
+    int cfg;            // WG_TAPS: tile (0 = 128 x 128, 2 = 64 x 64); WG_WS / WG_BF16X6: channel tiling of choose_wgrad_ws / choose_wgrad6
+    int S, per;         // splits; pixels per split (WG_WINO: 8-tile chunks per split)
+    int Npad, Cpad;     // dY x X channels of the partials
+    long long part;     // floats of weight partials
+    int bias_rows;      // bias-gradient partial rows the kernel leaves (0: the separate column-sum pass)
+};
+// tap-by-tap weight gradient (wgrad_kernel): the path every layer can take, and the one a smaller run-time batch falls back to
+static WgradPlan plan_wgrad_taps(const ConvGeom& g) {
     WeightMap wm; fg_geom_weightmap(g, &wm);
     const int st = g.stride == 2 ? 2 : 1;
-    const long long M = (long long)g.B * (g.H / st) * (g.W / st);
-    int wt, S, mper, Np, Cp, S6, mper6;
-    choose_wgrad(M, g.Cout, g.Cin, wm.G, wm.P, &wt, &S, &mper, &Np, &Cp);
-    long long n = (long long)wm.P * wm.G * S * Np * Cp;
-    if (M >= fg_wgrad_ws_minm() && choose_wgrad_ws(M, g.Cout, g.Cin, wm.G, wm.P, &S6, &mper6) >= 0) {
-        const long long n6 = (long long)wm.P * wm.G * S6 * g.Cout * g.Cin;
-        if (n6 > n) n = n6;
+    const long long M = (long long)g.B * (g.H / st) * (g.W / st);          // M-space = output pixels
+    WgradPlan p; memset(&p, 0, sizeof(p));
+    p.path = WG_TAPS;
+    choose_wgrad(M, g.Cout, g.Cin, wm.G, wm.P, &p.cfg, &p.S, &p.per, &p.Npad, &p.Cpad);
+    p.part = (long long)wm.P * wm.G * p.S * p.Npad * p.Cpad;
+    // bias gradient = column sums of gy over all output pixels: the kernel leaves them per (parity, split); ragged channel
+    // counts: the partial rows would be Nd wide -- the column-sum pass
+    p.bias_rows = (g.Cout % 4 || g.Cin % 4) ? 0 : wm.P * p.S;
+    return p;
+}
+static WgradPlan plan_wgrad(const ConvGeom& g, int math, int fusion) {
+    WeightMap wm; fg_geom_weightmap(g, &wm);
+    const int st = g.stride == 2 ? 2 : 1;
+    const int Hm = g.H / st, Wm = g.W / st;
+    const long long M = (long long)g.B * Hm * Wm;
+    const bool ragged = g.Cout % 4 || g.Cin % 4;
+    WgradPlan p; memset(&p, 0, sizeof(p));
+    p.Npad = g.Cout; p.Cpad = g.Cin;
+    // Winograd-domain weight gradient (wino_wgrad.hip): 16 instead of 36 / 9 / 25-of-36 multiplies per tile and channel pair
+    if ((fusion & FG_FUSE_WINOGRAD_WGRAD) && math != 6 && !ragged && choose_wino_wgrad(g, &p.S, &p.per)) {
+        p.path = WG_WINO;
+        p.part = wino_wgrad_part_floats(g, p.S);
+        p.bias_rows = wm.P * p.S;
+        return p;
     }
-    int Sw, cpsw;
-    if (choose_wino_wgrad(g, &Sw, &cpsw)) {      // (either setting of FG_FUSE_WINOGRAD_WGRAD: the bit is read per call)
-        const long long nw = wino_wgrad_part_floats(g, Sw);
-        if (nw > n) n = nw;
+    // bf16x6 (Linear / tiny maps: too few pixels to reduce over); the bias gradient takes the column-sum pass
+    if (math == 6 && g.Cout % 16 == 0 && g.Cin % 16 == 0 && M >= 1024 &&
+        (p.cfg = choose_wgrad6(M, g.Cout, g.Cin, wm.G, wm.P, &p.S, &p.per)) >= 0) {
+        p.path = WG_BF16X6;
+        p.part = (long long)wm.P * wm.G * p.S * g.Cout * g.Cin;
+        return p;
     }
+    // wave-specialised fp32 weight gradient (256 x 128 / 128 x 256 channel tiles, or 128 x 64 with the K-step split over the MFMA
+    // waves; one round of ~256 blocks) from 4096 pixels on; the bias gradient: the loader waves of the (X tile 0, tap 0) blocks
+    // leave per-channel sums of their dY rows, <= FG_WS_BIAS_ROWS_MAX of them (else the column-sum pass)
+    if (math != 6 && M >= 4096 && (p.cfg = choose_wgrad_ws(M, g.Cout, g.Cin, wm.G, wm.P, &p.S, &p.per)) >= 0) {
+        WgradArgs t; memset(&t, 0, sizeof(t));
+        t.M = (int)M; t.Hm = Hm; t.Wm = Wm; t.m_per_split = p.per; t.G = wm.G; t.Cpad = g.Cin;
+        t.lgH = ilog2_exact(Hm); t.lgW = ilog2_exact(Wm);
+        if (fg_wgrad_ws_shape_ok(t, p.cfg)) {
+            p.path = WG_WS;
+            p.part = (long long)wm.P * wm.G * p.S * g.Cout * g.Cin;
+            const long long rows = (long long)wm.P * p.S * fg_wgrad_ws_bias_rows(t, p.cfg);
+            p.bias_rows = rows <= FG_WS_BIAS_ROWS_MAX ? (int)rows : 0;
+            return p;
+        }
+    }
+    return plan_wgrad_taps(g);
+}
+// every weight-gradient plan a layer of this geometry can meet, in math mode `math` (-1: either): a live net can be switched between
+// the math modes and FG_FUSE_WINOGRAD_WGRAD on or off, and a smaller run-time batch can only fall back from the Winograd-domain to the
+// wave-specialised kernel (taken at this batch with the bit off) and from there or from bf16x6 to the tap-by-tap kernel
+static int wgrad_plans(const ConvGeom& g, int math, WgradPlan* out) {
+    int n = 0;
+    for (int m = 0; m <= 6; m += 6)
+        if (math < 0 || math == m) { out[n++] = plan_wgrad(g, m, FG_FUSE_WINOGRAD_WGRAD); out[n++] = plan_wgrad(g, m, 0); }
+    out[n++] = plan_wgrad_taps(g);
+    return n;
+}
+
+// floats of split-K / parity partials the fp32 weight gradient of this layer leaves: what the deferred-finals arena of a net
+// reserves per convolution so that the partials survive until the end of the backward pass (bf16x6 does not park them)
+long long fg_conv_wgrad_part_floats(const ConvGeom& g) {
+    WgradPlan p[5];
+    const int np = wgrad_plans(g, -1, p);
+    long long n = 0;
+    for (int i = 0; i < np; ++i)
+        if (p[i].path != WG_BF16X6 && p[i].part > n) n = p[i].part;
     return n + 64;
 }
 
-// floats of bias-gradient partial rows the fp32 weight gradient of this layer leaves for the deferred final (0: it takes the
-// separate column-sum pass) -- the same decisions as fg_conv_wgrad_run, for the arena of a net's workspace
+// floats of bias-gradient partial rows the weight gradient of this layer leaves for the deferred final, for the arena of a net's
+// workspace
 long long fg_conv_wgrad_bias_part_floats(const ConvGeom& g) {
-    WeightMap wm; fg_geom_weightmap(g, &wm);
-    const int st = g.stride == 2 ? 2 : 1;
-    const long long M = (long long)g.B * (g.H / st) * (g.W / st);
-    int wt, S, mper, Np, Cp;
-    choose_wgrad(M, g.Cout, g.Cin, wm.G, wm.P, &wt, &S, &mper, &Np, &Cp);
-    long long rows = (long long)wm.P * S;
-    {
-        int Sw, cpsw;
-        if (choose_wino_wgrad(g, &Sw, &cpsw) && (long long)wm.P * Sw > rows) rows = (long long)wm.P * Sw;
-    }
-    int S6, mper6;
-    const int cfg = M >= fg_wgrad_ws_minm() ? choose_wgrad_ws(M, g.Cout, g.Cin, wm.G, wm.P, &S6, &mper6) : -1;
-    if (cfg >= 0) {
-        WgradArgs a; memset(&a, 0, sizeof(a));
-        a.G = wm.G; a.Cpad = g.Cin;
-        const long long r = (long long)wm.P * S6 * fg_wgrad_ws_bias_rows(a, cfg);
-        if (r <= FG_WS_BIAS_ROWS_MAX && r > rows) rows = r;
-    }
+    WgradPlan p[5];
+    const int np = wgrad_plans(g, -1, p);
+    long long rows = 0;
+    for (int i = 0; i < np; ++i)
+        if (p[i].bias_rows > rows) rows = p[i].bias_rows;
     return rows * g.Cout + 64;
 }
 
@@ -356,7 +377,9 @@ static long long scratch_for_math(const ConvGeom& g, int math) {
         // (256 blocks x 64 tiles x 4 outputs x 64 channels: the block count already includes the four parities of a folded layer)
         if (need < 256LL * 64 * 4 * 64 + 64) need = 256LL * 64 * 4 * 64 + 64;
     } else {
-    choose_igemm(M, rf, wm.G * (cf / 32), wm.P, math, &tile, &splits);
+    // (where plan_igemm's bf16x6 falls back to an fp32 tile, its split partials stay below the 256 x 256 x 128 bound below; the
+    // planes are sized whatever the tile)
+    plan_igemm(M, rf, wm.G * (cf / 32), wm.P, math, fg_round_up(g.Cin, 4), cf, &tile, &splits);
     {
         long long n = splits > 1 ? (long long)splits * outM * g.Cout : 0;
         // bf16x6: a smaller run-time batch may pick split-K where the full batch does not; its partials are bounded by
@@ -369,7 +392,7 @@ static long long scratch_for_math(const ConvGeom& g, int math) {
         if (math == 6 && rf % 64 == 0) n += ((M * g.Cin + (long long)wm.P * wm.G * rf * cf) * 3 + 1) / 2 + 64;   // split planes
         if (n > need) need = n;
     }
-    choose_igemm(M, rb, wm.G * wm.P * (cb / 32), 1, math, &tile, &splits);
+    plan_igemm(M, rb, wm.G * wm.P * (cb / 32), 1, math, fg_round_up(g.Cout, 4), cb, &tile, &splits);
     {
         long long n = splits > 1 ? (long long)splits * M * g.Cin : 0;
         if (math == 6 && rb % 64 == 0 && n < 256LL * 256 * 128 + 64) n = 256LL * 256 * 128 + 64;
@@ -377,24 +400,17 @@ static long long scratch_for_math(const ConvGeom& g, int math) {
         if (n > need) need = n;
     }
     }
-    int wt, S, mper, Np, Cp;
-    choose_wgrad(M, g.Cout, g.Cin, wm.G, wm.P, &wt, &S, &mper, &Np, &Cp);
-    long long n3 = (long long)wm.P * wm.G * S * Np * Cp + (long long)wm.P * S * g.Cout;   // partials + bias-gradient partials
-    if (math == 6) {
-        int S6, mper6;
-        if (M >= 1024 && choose_wgrad6(M, g.Cout, g.Cin, wm.G, wm.P, &S6, &mper6) >= 0)
-            // Part + planes of gy and x, then (shared-plane backward) the data-gradient's split-K partials + weight planes
-            n3 = (long long)wm.P * wm.G * S6 * g.Cout * g.Cin + 4 + ((outM * g.Cout + M * g.Cin) * 3 + 1) / 2 + 64 +
-                 256LL * 256 * 128 + 64 + ((long long)wm.P * wm.G * rb * cb * 3 + 1) / 2 + 64;
+    // the weight gradient: its partials, then the bias-gradient partial rows (a call outside an fg_net backward pass has no
+    // deferred-finals arena); bf16x6: partials + planes of gy and x, then (shared-plane backward) the data-gradient's split-K
+    // partials + weight planes
+    WgradPlan wp[3];
+    const int np = wgrad_plans(g, math, wp);
+    for (int i = 0; i < np; ++i) {
+        const long long n = wp[i].path == WG_BF16X6
+            ? wp[i].part + 4 + ((outM * g.Cout + M * g.Cin) * 3 + 1) / 2 + 64 + 256LL * 256 * 128 + 64 + ((long long)wm.P * wm.G * rb * cb * 3 + 1) / 2 + 64
+            : wp[i].part + (long long)wp[i].bias_rows * g.Cout;
+        if (n > need) need = n;
     }
-    if (math != 6) {
-        // the default fp32 path runs wgrad_ws_kernel where it tiles (choose_wgrad_ws: its own split counts, up to 6 rounds of blocks):
-        // partials + the bias-gradient rows its loader waves leave (<= FG_WS_BIAS_ROWS_MAX rows) -- sized here explicitly, not by
-        // the accident that fg_conv_scratch_floats takes the maximum with the bf16x6 bound
-        const long long nws = fg_conv_wgrad_part_floats(g) + fg_conv_wgrad_bias_part_floats(g);
-        if (nws > n3) n3 = nws;
-    }
-    if (n3 > need) need = n3;
     long long n4 = (long long)(CR_ROWBLOCKS_MAX + 2) * g.Cout;
     if (n4 > need) need = n4;
     // ragged channel counts: the zero-padded copies of the operands (pad_operand) at the tail of the scratch
@@ -586,8 +602,7 @@ int fg_conv_forward_run(fg_ctx* ctx, const ConvGeom& g, const float* x, const fl
     }
     a.a_bytes = (long long)g.B * g.H * g.W * Ca * 4;
     int tile, splits;
-    choose_igemm(a.M, rf, wm.G * (cf / 32), wm.P, ctx->math, &tile, &splits);
-    if (tile == 4 && ctx->math == 6 && ((a.Ca % 16) || (a.Kpad % 16))) choose_igemm(a.M, rf, wm.G * (cf / 32), wm.P, 0, &tile, &splits);
+    plan_igemm(a.M, rf, wm.G * (cf / 32), wm.P, ctx->math, a.Ca, a.Kpad, &tile, &splits);
     const long long out_count = (long long)a.M * (g.fold ? 4 : 1) * g.Cout;
     a.splits = splits;
     if (splits > 1) {
@@ -696,8 +711,7 @@ int fg_conv_dgrad_run(fg_ctx* ctx, const ConvGeom& g, const float* gy, const flo
     }
     a.a_bytes = (long long)g.B * g.H * g.W * (g.fold ? 4 : 1) * Ca * 4;
     int tile, splits;
-    choose_igemm(a.M, rb, a.G * (cb / 32), 1, ctx->math, &tile, &splits);
-    if (tile == 4 && ctx->math == 6 && ((a.Ca % 16) || (a.Kpad % 16))) choose_igemm(a.M, rb, a.G * (cb / 32), 1, 0, &tile, &splits);
+    plan_igemm(a.M, rb, a.G * (cb / 32), 1, ctx->math, a.Ca, a.Kpad, &tile, &splits);
     const long long out_count = (long long)a.M * g.Cin;
     a.splits = splits;
     if (splits > 1) {
@@ -746,7 +760,6 @@ int fg_conv_wgrad_run(fg_ctx* ctx, const ConvGeom& g, const float* x, const floa
     if (rcp) return rcp;
     x = pad_operand(ctx, x, (long long)g.B * g.H * g.W, g.Cin, scratch, &scratch_floats, &Cx, &rcp);
     if (rcp) return rcp;
-    const bool ragged = Nd != g.Cout || Cx != g.Cin;
     a.dY = gy; a.X = x; a.Part = scratch;
     a.alg_flops = alg_flops(g); a.tag = tag_of(g, 2);
     a.Nb = g.B; a.Hm = g.H / st; a.Wm = g.W / st; a.M = g.B * a.Hm * a.Wm;          // M-space = output pixels
@@ -772,110 +785,61 @@ int fg_conv_wgrad_run(fg_ctx* ctx, const ConvGeom& g, const float* x, const floa
     }
     a.d_bytes = (long long)g.B * a.Hd * a.Wd * Nd * 4;
     a.x_bytes = (long long)g.B * g.H * g.W * Cx * 4;
-    int tile, rc;
-    int Sw, cpsw;
-    if ((ctx->fusion & FG_FUSE_WINOGRAD_WGRAD) && ctx->math != 6 && !ragged && choose_wino_wgrad(g, &Sw, &cpsw)) {
-        // Winograd-domain weight gradient (wino_wgrad.hip): 16 instead of 36 / 9 / 25-of-36 multiplies per tile and channel pair
-        WinoArgs wf; memset(&wf, 0, sizeof(wf));
-        fill_wino(wf, g, 0);
-        WinoWgradArgs w; memset(&w, 0, sizeof(w));
-        w.X = x; w.dY = gy; w.B = g.B; w.Hi = wf.Hi; w.Wi = wf.Wi; w.Cx = g.Cin; w.Ho = wf.Ho; w.Wo = wf.Wo; w.Nd = g.Cout;
-        w.TH = wf.TH; w.TW = wf.TW; w.T = wf.T; w.lgTH = wf.lgTH; w.lgTW = wf.lgTW;
-        w.isy = wf.isy; w.isx = wf.isx; w.KG = wf.KG; w.P = wf.P; w.osy = wf.osy; w.osx = wf.osx;
-        memcpy(w.goy, wf.goy, 4); memcpy(w.gox, wf.gox, 4); memcpy(w.ooy, wf.ooy, 4); memcpy(w.oox, wf.oox, 4);
-        w.S = Sw; w.chunks_per_split = cpsw; w.Npad = g.Cout; w.Cpad = g.Cin;
-        w.x_bytes = a.x_bytes; w.d_bytes = a.d_bytes; w.alg_flops = a.alg_flops; w.tag = a.tag;
-        const long long need = wino_wgrad_part_floats(g, Sw);
-        if (need > scratch_floats) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv wgrad (winograd): scratch %lld > %lld", need, scratch_floats);
-        const int nrb = w.P * Sw;
-        const long long nb = (long long)nrb * g.Cout;
-        bool deferred = false;
-        if (gradb) {
-            float* dp = fg_defer_alloc(ctx, nb);          // inside fg_net backward: final batched at the end
-            if (dp) { w.bias_part = dp; deferred = true; }
-            else if (need + nb <= scratch_floats) w.bias_part = scratch + need;
-        }
-        float* wp = fg_defer_parks_w(ctx) ? fg_defer_alloc(ctx, need) : nullptr;    // inside fg_net backward: summed at the end
-        w.Part = wp ? wp : scratch;
-        if ((rc = fg_launch_wino_wgrad(ctx, w))) return rc;
-        wm.wino = g.wino;                                  // the partials are Winograd-domain: the finish applies G^T . G and the tap scatter
-        if (!(wp && fg_defer_push_wfinish(ctx, wm, w.Part, Sw, w.Npad, w.Cpad, beta, gradW)) &&
-            (rc = fg_launch_wgrad_finish(ctx, wm, w.Part, Sw, w.Npad, w.Cpad, beta, gradW))) return rc;
-        if (gradb && w.bias_part) {
-            if (deferred) { fg_defer_push(ctx, w.bias_part, nrb, g.Cout, beta, gradb); return FG_OK; }
-            return fg_launch_colsum_final(ctx, w.bias_part, nrb, g.Cout, beta, gradb);
-        }
-        if (gradb) {
-            if ((long long)CR_ROWBLOCKS_MAX * g.Cout > scratch_floats) return fg_set_err(ctx, FG_ERR_WORKSPACE, "bias grad: scratch");
-            return fg_launch_colsum(ctx, gy_ref, (long long)a.M * (g.fold ? 4 : 1), g.Cout, beta, gradb, scratch);
-        }
-        return FG_OK;
-    }
-    int cfg6 = -1;
-    if (ctx->math == 6 && g.Cout % 16 == 0 && g.Cin % 16 == 0 && a.M >= 1024)   // Linear / tiny maps: too few pixels to reduce over
-        cfg6 = choose_wgrad6(a.M, g.Cout, g.Cin, wm.G, wm.P, &a.S, &a.m_per_split);
-    if (cfg6 >= 0) {
-        a.Npad = g.Cout; a.Cpad = g.Cin;
-        const long long part = ((long long)wm.P * wm.G * a.S * a.Npad * a.Cpad + 3) / 4 * 4;
+    const WgradPlan p = plan_wgrad(g, ctx->math, ctx->fusion);
+    a.S = p.S; a.m_per_split = p.per; a.Npad = p.Npad; a.Cpad = p.Cpad;
+    int rc;
+    if (p.path == WG_BF16X6) {
+        // the weight partials, then the split-bf16 planes of gy (kept for the data gradient: *gy6_out) and of x (unless the forward
+        // pass kept them); the partials are summed by the finish below, the bias gradient by the column-sum pass
+        const long long part = (p.part + 3) / 4 * 4;
         const long long d_fl = a.d_bytes / 4, x_fl = a.x_bytes / 4;
         const long long d6 = ((d_fl * 3 + 1) / 2 + 3) / 4 * 4, x6n = x6 ? 0 : (x_fl * 3 + 1) / 2;
         if (part + d6 + x6n > scratch_floats) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv wgrad (bf16x6): scratch %lld > %lld", part + d6 + x6n, scratch_floats);
         if ((rc = fg_launch_split_planes(ctx, gy, d_fl / g.Cout, g.Cout, scratch + part))) return rc;
         if (!x6 && (rc = fg_launch_split_planes(ctx, x, x_fl / g.Cin, g.Cin, scratch + part + d6))) return rc;
         a.D6 = scratch + part; a.X6 = x6 ? x6 : (const void*)(scratch + part + d6);
-        if ((rc = fg_launch_wgrad6(ctx, a, wm.P, cfg6))) return rc;
+        if ((rc = fg_launch_wgrad6(ctx, a, wm.P, p.cfg))) return rc;
         if (gy6_out) *gy6_out = a.D6;
         if (used_out) *used_out = part + d6;
-    } else if (fg_wgrad_ws_on() && ctx->math != 6 && a.M >= fg_wgrad_ws_minm() && choose_wgrad_ws(a.M, g.Cout, g.Cin, wm.G, wm.P, &a.S, &a.m_per_split) >= 0 &&
-               fg_wgrad_ws_shape_ok(a, choose_wgrad_ws(a.M, g.Cout, g.Cin, wm.G, wm.P, &a.S, &a.m_per_split))) {
-        // wave-specialised fp32 weight gradient (256 x 128 / 128 x 256 channel tiles, or 128 x 64 with the K-step split over the
-        // MFMA waves; one round of ~256 blocks); the bias gradient takes the separate column-sum pass at the end of this function
-        const int cfgw = choose_wgrad_ws(a.M, g.Cout, g.Cin, wm.G, wm.P, &a.S, &a.m_per_split);
-        a.Npad = g.Cout; a.Cpad = g.Cin;
-        const long long need = (long long)wm.P * wm.G * a.S * a.Npad * a.Cpad;
-        if (need > scratch_floats) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv wgrad (ws): scratch %lld > %lld", need, scratch_floats);
-        // bias gradient: the loader waves of the (X tile 0, tap 0) blocks leave per-channel sums of their dY rows
-        const int nrb = wm.P * a.S * fg_wgrad_ws_bias_rows(a, cfgw);
-        const long long nb = (long long)nrb * g.Cout;
-        bool deferred = false;
-        if (gradb && nrb <= FG_WS_BIAS_ROWS_MAX) {
-            float* dp = fg_defer_alloc(ctx, nb);          // inside fg_net backward: final batched at the end
-            if (dp) { a.bias_part = dp; deferred = true; }
-            else if (need + nb <= scratch_floats) a.bias_part = scratch + need;
-        }
-        float* wp = fg_defer_parks_w(ctx) ? fg_defer_alloc(ctx, need) : nullptr;    // inside fg_net backward: summed at the end
-        if (wp) a.Part = wp;
-        if ((rc = fg_launch_wgrad_ws(ctx, a, wm.P, cfgw))) return rc;
-        if (!(wp && fg_defer_push_wfinish(ctx, wm, a.Part, a.S, a.Npad, a.Cpad, beta, gradW)) &&
-            (rc = fg_launch_wgrad_finish(ctx, wm, a.Part, a.S, a.Npad, a.Cpad, beta, gradW))) return rc;
-        if (gradb && a.bias_part) {
-            if (deferred) { fg_defer_push(ctx, a.bias_part, nrb, g.Cout, beta, gradb); return FG_OK; }
-            return fg_launch_colsum_final(ctx, a.bias_part, nrb, g.Cout, beta, gradb);
-        }
+        if ((rc = fg_launch_wgrad_finish(ctx, wm, scratch, a.S, a.Npad, a.Cpad, beta, gradW))) return rc;
     } else {
-        choose_wgrad(a.M, g.Cout, g.Cin, wm.G, wm.P, &tile, &a.S, &a.m_per_split, &a.Npad, &a.Cpad);
-        const long long need = (long long)wm.P * wm.G * a.S * a.Npad * a.Cpad;
-        if (need > scratch_floats) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv wgrad: scratch %lld > %lld", need, scratch_floats);
-        // bias gradient = column sums of gy over all output pixels: the contraction kernel leaves them per (parity, split)
-        const int nrb = wm.P * a.S;
-        const long long nb = (long long)nrb * g.Cout;
+        if (p.part > scratch_floats) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv wgrad (%s): scratch %lld > %lld", wg_path_name[p.path], p.part, scratch_floats);
+        // the bias-gradient partial rows: in the deferred-finals arena inside an fg_net backward pass (final batched at the end),
+        // else behind the weight partials in the scratch, else none (the column-sum pass at the end of this function)
+        const long long nb = (long long)p.bias_rows * g.Cout;
+        float* bias_part = nullptr;
         bool deferred = false;
-        if (gradb && !ragged) {                          // (ragged: the partial rows would be Nd wide -- the column-sum pass below)
-            float* dp = fg_defer_alloc(ctx, nb);          // inside fg_net backward: final batched at the end
-            if (dp) { a.bias_part = dp; deferred = true; }
-            else if (need + nb <= scratch_floats) a.bias_part = scratch + need;
+        if (gradb && p.bias_rows) {
+            if ((bias_part = fg_defer_alloc(ctx, nb))) deferred = true;
+            else if (p.part + nb <= scratch_floats) bias_part = scratch + p.part;
         }
-        float* wp = fg_defer_parks_w(ctx) ? fg_defer_alloc(ctx, need) : nullptr;    // inside fg_net backward: summed at the end
-        if (wp) a.Part = wp;
-        if ((rc = fg_launch_wgrad(ctx, a, wm.P, tile))) return rc;
-        if (!(wp && fg_defer_push_wfinish(ctx, wm, a.Part, a.S, a.Npad, a.Cpad, beta, gradW)) &&
-            (rc = fg_launch_wgrad_finish(ctx, wm, a.Part, a.S, a.Npad, a.Cpad, beta, gradW))) return rc;
-        if (gradb && a.bias_part) {
-            if (deferred) { fg_defer_push(ctx, a.bias_part, nrb, g.Cout, beta, gradb); return FG_OK; }
-            return fg_launch_colsum_final(ctx, a.bias_part, nrb, g.Cout, beta, gradb);
+        float* wpark = fg_defer_parks_w(ctx) ? fg_defer_alloc(ctx, p.part) : nullptr;    // inside fg_net backward: summed at the end
+        float* part = wpark ? wpark : scratch;
+        if (p.path == WG_WINO) {
+            WinoArgs wf; memset(&wf, 0, sizeof(wf));
+            fill_wino(wf, g, 0);
+            WinoWgradArgs w; memset(&w, 0, sizeof(w));
+            w.X = x; w.dY = gy; w.B = g.B; w.Hi = wf.Hi; w.Wi = wf.Wi; w.Cx = g.Cin; w.Ho = wf.Ho; w.Wo = wf.Wo; w.Nd = g.Cout;
+            w.TH = wf.TH; w.TW = wf.TW; w.T = wf.T; w.lgTH = wf.lgTH; w.lgTW = wf.lgTW;
+            w.isy = wf.isy; w.isx = wf.isx; w.KG = wf.KG; w.P = wf.P; w.osy = wf.osy; w.osx = wf.osx;
+            memcpy(w.goy, wf.goy, 4); memcpy(w.gox, wf.gox, 4); memcpy(w.ooy, wf.ooy, 4); memcpy(w.oox, wf.oox, 4);
+            w.S = p.S; w.chunks_per_split = p.per; w.Npad = p.Npad; w.Cpad = p.Cpad;
+            w.x_bytes = a.x_bytes; w.d_bytes = a.d_bytes; w.alg_flops = a.alg_flops; w.tag = a.tag;
+            w.Part = part; w.bias_part = bias_part;
+            rc = fg_launch_wino_wgrad(ctx, w);
+            wm.wino = g.wino;                              // the partials are Winograd-domain: the finish applies G^T . G and the tap scatter
+        } else {
+            a.Part = part; a.bias_part = bias_part;
+            rc = p.path == WG_WS ? fg_launch_wgrad_ws(ctx, a, wm.P, p.cfg) : fg_launch_wgrad(ctx, a, wm.P, p.cfg);
+        }
+        if (rc) return rc;
+        if (!(wpark && fg_defer_push_wfinish(ctx, wm, part, p.S, p.Npad, p.Cpad, beta, gradW)) &&
+            (rc = fg_launch_wgrad_finish(ctx, wm, part, p.S, p.Npad, p.Cpad, beta, gradW))) return rc;
+        if (bias_part) {
+            if (deferred) { fg_defer_push(ctx, bias_part, p.bias_rows, g.Cout, beta, gradb); return FG_OK; }
+            return fg_launch_colsum_final(ctx, bias_part, p.bias_rows, g.Cout, beta, gradb);
         }
     }
-    if (cfg6 >= 0 && (rc = fg_launch_wgrad_finish(ctx, wm, scratch, a.S, a.Npad, a.Cpad, beta, gradW))) return rc;
     if (gradb) {
         // bias grad = column sums of gy over all output pixels
         const long long rows = (long long)a.M * (g.fold ? 4 : 1);

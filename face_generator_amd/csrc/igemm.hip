@@ -694,11 +694,6 @@ static bool fg_ws_trace_on() {
     return on != 0;
 }
 #endif   // FG_MEASURE
-static bool fg_ws64_ns3() {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("FG_IGEMM_WS64_NS3"); on = e ? atoi(e) : 1; }
-    return on != 0;
-}
 static int launch_igemm_ws64x3(fg_ctx* ctx, const IgemmArgs& a, int P) {
     const size_t lds = (size_t)(3 * (WS_BM + 64) * WS_LDK + WS_BM) * sizeof(float);
     static char attr_key;                      // one key per call site (and template instance); the flag lives in the context
@@ -722,9 +717,9 @@ static int launch_igemm_ws64x3(fg_ctx* ctx, const IgemmArgs& a, int P) {
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }
-template <int BN>
+// 256 x 128 tiles on a 4-stage ring (the layers with 64 output channels take launch_igemm_ws64x3)
 static int launch_igemm_ws(fg_ctx* ctx, const IgemmArgs& a, int P) {
-    if (BN == 64 && fg_ws64_ns3()) return launch_igemm_ws64x3(ctx, a, P);
+    constexpr int BN = WS_BN;
     const size_t lds = (size_t)(WS_NS * (WS_BM + BN) * WS_LDK + WS_BM) * sizeof(float);
     static char attr_key;                      // one key per call site (and template instance); the flag lives in the context
     if (fg_attr_first(ctx, &attr_key)) {
@@ -736,7 +731,7 @@ static int launch_igemm_ws(fg_ctx* ctx, const IgemmArgs& a, int P) {
     const double exec = 2.0 * (double)grid.x * WS_BM * BN * (double)a.G * a.Kpad;
     const int epi = a.act_x ? 2 : (a.act_y ? 1 : 0);
 #ifdef FG_MEASURE
-    if (BN == 128 && fg_ws_trace_on() && epi == 0 && !a.stats_part) return fg_ws_trace_launch(ctx, a, 128, grid, lds);
+    if (fg_ws_trace_on() && epi == 0 && !a.stats_part) return fg_ws_trace_launch(ctx, a, BN, grid, lds);
 #endif
     char label[96];
     if (epi) snprintf(label, sizeof(label), "igemm_ws_act_kernel<%d,%d>/%s", BN, epi, a.tag ? a.tag : "?");
@@ -1086,17 +1081,15 @@ int fg_launch_igemm(fg_ctx* ctx, const IgemmArgs& a_in, int P, int tile) {
         case 2: {
             if (a.Npad % 64) break;
             // 64-deep K-steps (half the barriers, 70 KB of LDS: still two blocks per CU) where the padded K allows: D's mid-size
-            // convolutions 56.7 -> 54.7 us, G's first data gradient 199.8 -> 193.8 (FG_IGEMM_BK64=0 switches back)
-            static int bk64 = -1;
-            if (bk64 < 0) { const char* e = getenv("FG_IGEMM_BK64"); bk64 = e ? atoi(e) : 1; }
-            if (bk64 && a.Kpad % 64 == 0 && ((a.G * (a.Kpad / 64)) % a.splits == 0)) return launch_igemm_t<64, 64, 64>(ctx, a, P);
+            // convolutions 56.7 -> 54.7 us, G's first data gradient 199.8 -> 193.8
+            if (a.Kpad % 64 == 0 && ((a.G * (a.Kpad / 64)) % a.splits == 0)) return launch_igemm_t<64, 64, 64>(ctx, a, P);
             return launch_igemm_t<64, 64, 32>(ctx, a, P);
         }
-        case 5: if (a.Npad % 64 || a.A6) break; return launch_igemm_ws<64>(ctx, a, P);
+        case 5: if (a.Npad % 64 || a.A6) break; return launch_igemm_ws64x3(ctx, a, P);
         case 4:
             if (a.A6) { if (a.Npad % 64) break; return (a.Npad % 128 == 0) ? launch_igemm_ws6<128>(ctx, a, P) : launch_igemm_ws6<64>(ctx, a, P); }
             if (a.Npad % 64) break;
-            return (a.Npad % 128 == 0) ? launch_igemm_ws<128>(ctx, a, P) : launch_igemm_ws<64>(ctx, a, P);
+            return (a.Npad % 128 == 0) ? launch_igemm_ws(ctx, a, P) : launch_igemm_ws64x3(ctx, a, P);
     }
     return fg_set_err(ctx, FG_ERR_INVALID, "igemm: bad tile %d for Npad %d", tile, a.Npad);
 }
@@ -1494,11 +1487,8 @@ int fg_launch_wgrad(fg_ctx* ctx, const WgradArgs& a, int P, int tile) {
     // (the 64-tile is the other way round: 89 vs 106 TFLOP/s at 16 vs 32 pixels, and better again at 64)
     if (tile == 0 && a.Npad % 128 == 0 && a.Cpad % 128 == 0) return launch_wgrad_t<128, 16, 4>(ctx, a, P);
     // the 64-tile (one accumulator tile per wave) wants LONG K-steps: 64 pixels 687 us, 32 pixels 737 us, 16 pixels slower
-    // still on the c2f 64-channel layers (FG_WGRAD64_BK=32 switches back)
-    static int w64 = -1;
-    if (w64 < 0) { const char* e = getenv("FG_WGRAD64_BK"); w64 = e ? atoi(e) : 64; }
-    if (tile == 2 && a.Npad % 64 == 0 && a.Cpad % 64 == 0 && w64 == 64 && a.m_per_split % 64 == 0) return launch_wgrad_t<64, 64, 2>(ctx, a, P);
-    if (tile == 2 && a.Npad % 64 == 0 && a.Cpad % 64 == 0) return launch_wgrad_t<64, 32, 2>(ctx, a, P);
+    // still on the c2f 64-channel layers (choose_wgrad gives it whole 64-pixel steps per split)
+    if (tile == 2 && a.Npad % 64 == 0 && a.Cpad % 64 == 0 && a.m_per_split % 64 == 0) return launch_wgrad_t<64, 64, 2>(ctx, a, P);
     return fg_set_err(ctx, FG_ERR_INVALID, "wgrad: bad tile %d for %dx%d", tile, a.Npad, a.Cpad);
 }
 

@@ -626,12 +626,10 @@ int fg_net_create(fg_ctx* ctx, const fg_layer_spec* L, int nl, int in_c, int in_
                 s.slope_off = poff; poff += 1;
                 n->layers[i].w_off = s.slope_off; n->layers[i].w_n = 1;
                 s.has_prelu = 1; s.oc = c; s.oh = h; s.ow = w;
-                static int amp_on = -1;      // A/B switch (round 4; default on): FG_ACTMAXPOOL=0 keeps PReLU / MaxPool / Dropout apart
-                if (amp_on < 0) { const char* e = getenv("FG_ACTMAXPOOL"); amp_on = e ? atoi(e) : 1; }
                 if (i + 2 < nl && L[i + 1].type == FG_SPATIAL_DROPOUT && L[i + 2].type == FG_AVGPOOL2 && c % 4 == 0 &&
                     h % 2 == 0 && w % 2 == 0) {
                     s.kind = ST_ACTPOOL; s.p = L[i + 1].p; s.mask_kind = 1; s.oh = h / 2; s.ow = w / 2; consumed = 3;
-                } else if (amp_on && i + 1 < nl && L[i + 1].type == FG_MAXPOOL2 && c % 4 == 0 && h % 2 == 0 && w % 2 == 0 && i > 0) {
+                } else if (i + 1 < nl && L[i + 1].type == FG_MAXPOOL2 && c % 4 == 0 && h % 2 == 0 && w % 2 == 0 && i > 0) {
                     // PReLU -> MaxPool [-> Dropout]: the pooled (and masked) tensor is all the next layer reads, prelu(x) at full
                     // resolution is never materialised (the producing layer stores x alone); backward re-evaluates it from x
                     s.kind = ST_ACTMAXPOOL; s.oh = h / 2; s.ow = w / 2; consumed = 2;

@@ -624,13 +624,6 @@ __global__ __launch_bounds__(256) void thin_in_mfma_pad_kernel(const float* __re
     }
     if constexpr (EPI == 2) thin_epi_finish(epi, es, lane, wave);
 }
-// A/B switch (round 3; default on): FG_THIN_PADDED=0 keeps the bounds-checked gathers of the 5x5 / 7x7 thin kernels
-static bool fg_thin_padded_on() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("FG_THIN_PADDED"); v = e ? atoi(e) : 1; }
-    return v != 0;
-}
-
 int fg_launch_thin_in_conv(fg_ctx* ctx, const float* in, const float* Wp, const float* bias, float* out, int B, int H,
                            int W, int Cs, int Cw, int k, int flip, const FgActFuse* actf, const FgActBwd* actb,
                            float* padbuf, long long padbuf_floats) {
@@ -708,8 +701,7 @@ int fg_launch_thin_in_conv(fg_ctx* ctx, const float* in, const float* Wp, const 
         {   // 5x5 / 7x7 on power-of-two maps with room for a zero-bordered copy of the input: no gather arithmetic at all
             const int pad = (k - 1) / 2;
             const long long padf = (long long)B * (H + 2 * pad) * (W + 2 * pad) * Cs;
-            if (k >= 5 && lgH >= 0 && lgW >= 0 && padbuf && padf <= padbuf_floats && padf < (1LL << 28) && (long long)npix * Cw * 4 < 0x7FFFFFF0LL &&
-                fg_thin_padded_on()) {
+            if (k >= 5 && lgH >= 0 && lgW >= 0 && padbuf && padf <= padbuf_floats && padf < (1LL << 28) && (long long)npix * Cw * 4 < 0x7FFFFFF0LL) {
                 const int rcp = fg_launch_thin_pad(ctx, in, padbuf, B, H, W, Cs, pad);
                 if (rcp) return rcp;
 #define TIP(KK, CC)                                                                                                  \
@@ -1600,8 +1592,6 @@ __global__ __launch_bounds__(256) void thin_wgrad_mfma_kernel(const float* __res
     }
 }
 
-static bool fg_thin_wgrad_padded_on() { return fg_thin_padded_on(); }
-
 // wide_colsum (optional): receives sum_pix wide[pix][c] (beta = 0) from the ones column of the matrix-pipe kernels; *colsum_done
 // tells the caller whether it was produced (the VALU fallback kernels do not).  With it the slabs have k*k*Cs + 1 rows: `scratch`
 // holds FG_THIN_WGRAD_BLOCKS * (k*k*Cs + 1) * Cw floats for them.
@@ -1641,7 +1631,7 @@ int fg_launch_thin_wgrad(fg_ctx* ctx, const float* thin, const float* wide, floa
         const bool fits = (long long)B * H * W * Cw < (1LL << 31);
         // 5x5 / 7x7 on power-of-two maps: gather from a zero-bordered copy of the thin tensor kept in the tail of the slab area
         // (the layer's slabs are large: the copy displaces a few of the TW_BLOCKS blocks)
-        if (fits && k >= 5 && lgH >= 0 && lgW >= 0 && (Cs == 1 || Cs == 3) && fg_thin_wgrad_padded_on()) {
+        if (fits && k >= 5 && lgH >= 0 && lgW >= 0 && (Cs == 1 || Cs == 3)) {
             const int pad = (k - 1) / 2;
             const long long slab = (long long)NR * Cw, padf = (long long)B * (H + 2 * pad) * (W + 2 * pad) * Cs;
             const long long take = (padf + slab - 1) / slab;

@@ -101,8 +101,8 @@ int fg_set_fusion(fg_ctx* ctx, int flags);
 int fg_get_fusion(fg_ctx* ctx);
 /* Test hook (parity tests only; replaces nothing in the reference): the two planning thresholds that decide where the Winograd-domain
  * weight gradient is taken -- at least `min_chunks` eight-tile chunks per block and `min_blocks` blocks per launch (defaults 24, 192;
- * <= 0 restores a default).  Process-wide; also read ONCE from FG_WINO_WGRAD_MIN_CHUNKS / FG_WINO_WGRAD_MIN_BLOCKS at the first
- * fg_ctx_create.  Lets small shapes reach the kernel's corners (one chunk, ragged last chunk, a single channel block). */
+ * <= 0 restores a default).  Process-wide, and the only way to change them: no environment variable does.  Lets small shapes reach
+ * the kernel's corners (one chunk, ragged last chunk, a single channel block). */
 int fg_test_set_wino_wgrad_thresholds(fg_ctx* ctx, long long min_chunks, long long min_blocks);
 
 /* ---- context / memory (replaces cutorch.setDevice / cutorch streams, train.lua:79-80) ----

@@ -49,6 +49,43 @@ def test_default_library_has_no_trace_or_wrong_result_variants(lib):
     assert "getenv" not in body
 
 
+REMOVED_SWITCHES = {"FG_IGEMM_WS", "FG_LINEAR_FWD128", "FG_LINEAR_WGRAD64", "FG_WGRAD_ROUNDS", "FG_WGRAD_WS64", "FG_WGRAD_WS_MINM",
+                    "FG_WGRAD_WS", "FG_WINO_WGRAD_MIN_CHUNKS", "FG_WINO_WGRAD_MIN_BLOCKS", "FG_IGEMM_WS64_NS3", "FG_IGEMM_BK64",
+                    "FG_WGRAD64_BK", "FG_THIN_PADDED", "FG_ACTMAXPOOL"}
+
+
+def _outside_measure_blocks(src):
+    """The lines of a source file the default build compiles: everything but the FG_MEASURE branches of #ifdef blocks."""
+    keep, stack = [], []          # stack: per open #if, whether its current branch is measurement-only
+    for line in src.splitlines():
+        d = line.strip()
+        if d.startswith("#if"):
+            stack.append(d.split("//")[0].split() == ["#ifdef", "FG_MEASURE"])
+        elif d.startswith("#else"):
+            stack[-1] = not stack[-1]
+        elif d.startswith("#endif"):
+            stack.pop()
+        elif not any(stack):
+            keep.append(line)
+    assert not stack, "unbalanced #if / #endif"
+    return "\n".join(keep)
+
+
+def test_default_library_has_no_ab_switches(lib):
+    """Kernel choices are made by the shapes, the math mode and the per-context fusion bits, never by a process-wide environment
+    variable: the removed A/B switches are not in the library's string table, and outside the measurement build only context
+    creation (api.hip: FG_LAUNCH_LOG, FG_MATH, the FG_FUSE_* aliases) and the RCCL loader (step.hip: FG_RCCL_LIB) read the
+    environment."""
+    from face_generator_amd import _lib
+    blob = open(_lib.lib_path(), "rb").read()
+    names = set(m.decode() for m in re.findall(rb"FG_[A-Z0-9_]+", blob))
+    assert names & REMOVED_SWITCHES == set(), sorted(names & REMOVED_SWITCHES)
+    csrc = os.path.join(ROOT, "face_generator_amd", "csrc")
+    readers = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".cpp"))
+                     and "getenv" in _outside_measure_blocks(open(os.path.join(csrc, f)).read()))
+    assert readers == ["api.hip", "step.hip"], readers
+
+
 def test_no_gpu_fails_loudly_not_silently(lib):
     if torch.cuda.is_available():
         pytest.skip("GPU present")
