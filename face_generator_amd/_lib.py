@@ -14,7 +14,7 @@ FG_BWD_PARAM_GRADS = 1
 FG_BWD_INPUT_GRAD = 2
 
 LAYER_TYPES = dict(LINEAR=1, VIEW=2, PRELU=3, UPSAMPLE2X=4, CONV=5, BATCHNORM=6, SPATIAL_DROPOUT=7, AVGPOOL2=8,
-                   DROPOUT=9, SIGMOID=10, LEAKYRELU=11, MAXPOOL2=12)
+                   DROPOUT=9, SIGMOID=10, LEAKYRELU=11, MAXPOOL2=12, CONCAT_TABLE=13, BRANCH=14, JOIN_TABLE=15)
 
 
 class FgError(RuntimeError):
@@ -28,7 +28,7 @@ class LayerSpec(ctypes.Structure):
 
 _CTYPES = [
     (r"^const fg_layer_spec\*$", ctypes.POINTER(LayerSpec)),
-    (r"^const float\* const\*$", ctypes.POINTER(ctypes.c_void_p)),
+    (r"^(const )?float\* const\*$", ctypes.POINTER(ctypes.c_void_p)),
     (r"^(fg_ctx|fg_net|fg_comm|fg_gan|void|float)\*\*$", ctypes.POINTER(ctypes.c_void_p)),
     (r"^const char\*$", ctypes.c_char_p),
     (r"^char\*$", ctypes.c_char_p),

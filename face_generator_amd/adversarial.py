@@ -61,7 +61,8 @@ class Trainer:
     def _make_fused(self):
         """The step-level C entries (fg_step_D / fg_step_G) carry the closure whenever both nets are single compiled plans
         and the exchange carrier is the library's own communicator (or there is none).  The module-by-module host path
-        below stays for ConcatTable nets (create_D16_d) and for torch.distributed carriers (gloo in the CPU / one-GPU tests)."""
+        below stays for nets walked from Python (ConcatSequential.cuda(composite=True), the c2f table nets without a step object)
+        and for torch.distributed carriers (gloo in the CPU / one-GPU tests)."""
         from .runtime import DeviceNet, FusedGan
         from .distributed import FgCollective
         if not (isinstance(self.dnG, DeviceNet) and isinstance(self.dnD, DeviceNet)):

@@ -535,6 +535,34 @@ int fg_add(fg_ctx* ctx, const float* a, const float* b, float* out, long long n)
     NEED(ctx, ctx && a && b && out && n >= 0, "bad argument");
     return fg_launch_add(ctx, a, b, out, n);
 }
+static int row_parts(fg_ctx* ctx, const float* const* parts, const int* widths, int n, bool need_all, FgRowParts* out) {
+    NEED(ctx, ctx && parts && n >= 1 && n <= FG_TABLE_MAX, "1 to 4 parts");
+    memset(out, 0, sizeof(*out));
+    out->n = n;
+    for (int i = 0; i < n; ++i) {
+        NEED(ctx, (parts[i] || !need_all) && (!widths || widths[i] > 0), "null part / width <= 0");
+        out->p[i] = (float*)parts[i]; out->w[i] = widths ? widths[i] : 0;
+    }
+    return FG_OK;
+}
+int fg_join_rows(fg_ctx* ctx, const float* const* parts, const int* widths, int n, float* out, int rows) {
+    FgRowParts a;
+    NEED(ctx, ctx && out && widths && rows >= 0, "bad argument");
+    const int rc = row_parts(ctx, parts, widths, n, true, &a);
+    return rc ? rc : fg_launch_join_rows(ctx, a, out, rows);
+}
+int fg_split_rows(fg_ctx* ctx, const float* g, float* const* parts, const int* widths, int n, int rows) {
+    FgRowParts a;
+    NEED(ctx, ctx && g && widths && rows >= 0, "bad argument");
+    const int rc = row_parts(ctx, parts, widths, n, false, &a);
+    return rc ? rc : fg_launch_split_rows(ctx, g, a, rows);
+}
+int fg_sum_n(fg_ctx* ctx, const float* const* parts, int n, float* out, long long count) {
+    FgRowParts a;
+    NEED(ctx, ctx && out && count >= 0, "bad argument");
+    const int rc = row_parts(ctx, parts, nullptr, n, true, &a);
+    return rc ? rc : fg_launch_sum_parts(ctx, a, out, count);
+}
 int fg_sigmoid_forward(fg_ctx* ctx, const float* x, float* y, long long n) { NEED(ctx, ctx && x && y, "null argument"); return fg_launch_sigmoid_forward(ctx, x, y, n); }
 int fg_sigmoid_backward(fg_ctx* ctx, const float* y, const float* gy, float* gx, long long n) {
     NEED(ctx, ctx && y && gy && gx, "null argument");

@@ -406,6 +406,13 @@ int fg_launch_concat(fg_ctx*, const float* a, const float* b, float* out, long l
 int fg_launch_split(fg_ctx*, const float* g, float* ga, float* gb, long long npix, int ca, int cb);
 int fg_launch_add(fg_ctx*, const float* a, const float* b, float* out, long long n);
 int fg_launch_copy(fg_ctx*, const float* src, float* dst, long long n);
+// nn.ConcatTable inside a compiled net: up to FG_TABLE_MAX branches.  join: out[r][off_k + j] = p[k][r][j]; split: the reverse (a null
+// p[k] is skipped); sum: out = ((p[0] + p[1]) + p[2]) + p[3].  One launch each.
+#define FG_TABLE_MAX 4
+struct FgRowParts { float* p[FG_TABLE_MAX]; int w[FG_TABLE_MAX]; int n; };
+int fg_launch_join_rows(fg_ctx*, const FgRowParts& parts, float* out, int rows);
+int fg_launch_split_rows(fg_ctx*, const float* g, const FgRowParts& parts, int rows);
+int fg_launch_sum_parts(fg_ctx*, const FgRowParts& parts, float* out, long long n);
 int fg_launch_add_halves(fg_ctx*, const float* a0, const float* b0, const float* a1, const float* b1, float* out, long long nh);
 // deferred finals: partial buffer of `floats` floats (nullptr = not deferring / arena full -> caller uses its scratch and an
 // immediate final); registration of one final job; flush = run all registered jobs in one launch

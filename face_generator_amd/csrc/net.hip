@@ -29,12 +29,20 @@ enum StageKind {
     ST_SDROPOUT,
     ST_MAXPOOL,
     ST_DROPOUT,       // standalone nn.Dropout (any shape)
-    ST_REVIEW         // the flat NCHW re-view behind a SpatialConvolutionUpsample with factor > 1
+    ST_REVIEW,        // the flat NCHW re-view behind a SpatialConvolutionUpsample with factor > 1
+    ST_JOIN           // nn.JoinTable(2) closing an nn.ConcatTable: the branches' feature vectors side by side (models.lua:305-312)
 };
 
 struct Stage {
     int kind = 0;
     int first_layer = 0, last_layer = 0;
+    // the plan of an nn.ConcatTable net stays a linear list, [branch 1][branch 2]...[join][tail]: a stage records where its input
+    // comes from.  src = index of the producing stage (the previous one in a chain), -1 = the net's input (stage 0 and the first
+    // stage of every branch), -2 = ST_JOIN (reads the last stage of every branch).  Nothing is fused across a stage whose src is
+    // not its predecessor.
+    int src = -1;
+    int head_of = -1;         // first stage of branch k: its input gradient goes to that branch's buffer (summed behind stage 0)
+    int branch_end = -1;      // last stage of branch k: its output gradient is slice k of the split joined gradient
     int ic = 0, ih = 0, iw = 0, oc = 0, oh = 0, ow = 0;
     long long w_off = -1, w_n = 0, b_off = -1, b_n = 0;
     long long slope_off = -1, gamma_off = -1, beta_off = -1, buf_off = -1;
@@ -111,6 +119,10 @@ struct fg_net {
     bool adam_fusable = false;
     long long pack_lds_floats = 64;   // dynamic shared memory of the re-pack launch: the largest staging area any of its jobs needs
     bool park_w = true;               // FG_FUSE_WFINISH_BATCH at creation: the workspace reserves room for parked weight-gradient partials
+    // nn.ConcatTable: branch widths, the slices the backward split writes and the per-branch input gradients (workspace offsets)
+    int n_branch = 0;
+    int br_last[FG_TABLE_MAX] = {0, 0, 0, 0}, br_w[FG_TABLE_MAX] = {0, 0, 0, 0};
+    long long gsplit_off[FG_TABLE_MAX] = {0, 0, 0, 0}, gin_off[FG_TABLE_MAX] = {0, 0, 0, 0};
 };
 
 static inline long long align64(long long v) { return (v + 63) / 64 * 64; }
@@ -140,6 +152,8 @@ static void make_plan(fg_net* n, int B) {
         s.out_off = off; off += align64(osz);
         s.aux_off = off;
         if (s.kind == ST_BNPRELU) off += align64(2 * s.oc);
+        if (s.kind == ST_JOIN)
+            for (int k = 0; k < n->n_branch; ++k) { n->gsplit_off[k] = off; off += align64((long long)B * n->br_w[k]); }
         if (s.kind == ST_BNPRELU && &s != &n->st[0] && (&s)[-1].kind == ST_CONV) {
             s.stats_cap = 2 * ((long long)B * s.ih * s.iw / 32 + 16) * s.ic;     // >= 2 x (wave rows of any tiling) x C
             s.stats_off = off; off += align64(s.stats_cap);
@@ -180,6 +194,7 @@ static void make_plan(fg_net* n, int B) {
         }
         n->defer_off = off; n->defer_floats = dn; off += align64(dn);
     }
+    for (int k = 0; k < n->n_branch; ++k) { n->gin_off[k] = off; off += align64((long long)B * n->in_c * n->in_h * n->in_w); }
     n->grad_off[0] = off; off += align64(maxact);
     n->grad_off[1] = off; off += align64(maxact);
     n->tmp_off = off; off += align64(maxact);
@@ -209,11 +224,14 @@ static int backward_run_stages(fg_net* n) {
     for (int si = n->run_stage; si >= stage_to; --si) {
         Stage& s = n->st[si];
         if (prelu_folded) { prelu_folded = false; continue; }      // gcur already is the gradient wrt the PReLU's input
+        if (s.branch_end >= 0) gcur = ws + n->gsplit_off[s.branch_end];      // left by the join stage's split
+        const bool chained = s.src == si - 1;        // the previous stage of the list produced this stage's input
         if (s.kind != ST_ACTPOOL) n->pend.splits = 0;
         // a plain PReLU directly in front of this stage (inside this call's range, not the net's first stage): its backward
         // can ride on the epilogue of the kernel that produces this stage's input gradient
         FgActBwd actb; memset(&actb, 0, sizeof(actb));
-        const bool pf = si >= 2 && si - 1 >= stage_to && n->st[si - 1].kind == ST_PRELU && n->st[si - 1].mask_kind != 1 &&
+        const bool pf = si >= 2 && si - 1 >= stage_to && chained && n->st[si - 1].src == si - 2 &&
+                        n->st[si - 1].kind == ST_PRELU && n->st[si - 1].mask_kind != 1 &&
                         fg_fuse_prelu(ctx);
         if (pf) {
             const Stage& ps = n->st[si - 1];
@@ -221,10 +239,10 @@ static int backward_run_stages(fg_net* n) {
             actb.gslope = want_p ? Gp + ps.slope_off : nullptr;
             if (ps.mask_kind == 2) { actb.mask = n->mask_ptrs[ps.mask_idx]; actb.mscale = 1.f / (1.f - ps.p); }   // PReLU + Dropout
         }
-        const float* xin = si == 0 ? x : ws + n->st[si - 1].out_off;
+        const float* xin = s.src < 0 ? x : ws + n->st[s.src].out_off;
         const float* yout = (si + 1 == (int)n->st.size() && n->out_override) ? n->out_override : ws + s.out_off;
-        const bool need_gx = si > 0 || want_x;
-        float* gxb = si == 0 ? gx : ws + n->grad_off[pp];
+        const bool need_gx = s.src != -1 || want_x;
+        float* gxb = s.head_of >= 0 ? ws + n->gin_off[s.head_of] : si == 0 ? gx : ws + n->grad_off[pp];
         if (!need_gx) gxb = nullptr;
         const float* mask = (s.mask_idx >= 0) ? n->mask_ptrs[s.mask_idx] : nullptr;
         switch (s.kind) {
@@ -248,7 +266,7 @@ static int backward_run_stages(fg_net* n) {
                     }
                 }
                 // the fused PReLU + SpatialDropout + AvgPool backward in front of this layer sums split-K partials itself
-                const bool ap = si >= 1 && si - 1 >= stage_to && n->st[si - 1].kind == ST_ACTPOOL && fg_fuse_prelu(ctx);
+                const bool ap = si >= 1 && si - 1 >= stage_to && chained && n->st[si - 1].kind == ST_ACTPOOL && fg_fuse_prelu(ctx);
                 n->pend.splits = 0;
                 if (!rc && need_gx) rc = fg_conv_dgrad_run(ctx, g, gcur, s.wp_bwd, gxb, scratch + gy6_used, n->scratch_floats - gy6_used,
                                                          n->planes_valid ? s.wp_bwd6 : nullptr, gy6, pf ? &actb : nullptr,
@@ -359,7 +377,20 @@ static int backward_run_stages(fg_net* n) {
             case ST_DROPOUT:
                 if (need_gx) rc = fg_launch_mul_mask(ctx, gcur, mask, 1.f / (1.f - s.p), gxb, (long long)B * s.ic * s.ih * s.iw);
                 break;
+            case ST_JOIN: {           // the joined gradient -> one contiguous slice per branch
+                FgRowParts a; memset(&a, 0, sizeof(a));
+                a.n = n->n_branch;
+                for (int k = 0; k < a.n; ++k) { a.p[k] = ws + n->gsplit_off[k]; a.w[k] = n->br_w[k]; }
+                rc = fg_launch_split_rows(ctx, gcur, a, B);
+                break;
+            }
             default: rc = fg_set_err(ctx, FG_ERR_INVALID, "fg_net_backward: bad stage kind %d", s.kind);
+        }
+        if (!rc && si == 0 && n->n_branch && want_x) {      // nn.ConcatTable: gradInput = ((branch 1 + branch 2) + branch 3) + branch 4
+            FgRowParts a; memset(&a, 0, sizeof(a));
+            a.n = n->n_branch;
+            for (int k = 0; k < a.n; ++k) a.p[k] = ws + n->gin_off[k];
+            rc = fg_launch_sum_parts(ctx, a, gx, (long long)B * n->in_c * n->in_h * n->in_w);
         }
         if (rc) return rc;
         gcur = gxb;
@@ -380,6 +411,8 @@ static int forward_run(fg_net* n, long long* out_offset) {
     for (int si = n->run_stage; si < (int)n->st.size(); ++si) {
         Stage& s = n->st[si];
         if (s.kind != ST_ACTPOOL) n->pend.splits = 0;
+        if (s.src == -1) cur = n->run_x;       // stage 0 and the first stage of every branch
+        const bool has_next = si + 1 < (int)n->st.size() && n->st[si + 1].src == si;     // the next stage of the list reads this one
         float* y = (si + 1 == (int)n->st.size() && n->out_override) ? n->out_override : ws + s.out_off;
         const float* mask = (s.mask_idx >= 0) ? n->mask_ptrs[s.mask_idx] : nullptr;
         switch (s.kind) {
@@ -387,12 +420,12 @@ static int forward_run(fg_net* n, long long* out_offset) {
                 ConvGeom g = s.geom; g.B = B;
                 s.x6_valid = 0;
                 // a BatchNorm directly behind this convolution takes its batch statistics from the epilogue
-                Stage* bn = (train && !n->sync_bn && si + 1 < (int)n->st.size() && n->st[si + 1].kind == ST_BNPRELU &&
+                Stage* bn = (train && !n->sync_bn && has_next && n->st[si + 1].kind == ST_BNPRELU &&
                              n->st[si + 1].stats_off >= 0) ? &n->st[si + 1] : nullptr;
                 if (bn) bn->stats_rows = 0;
                 // a PReLU [+ Dropout] directly behind a split-K layer (the Linear layers) rides on the pass that sums the splits
                 FgActFuse act; memset(&act, 0, sizeof(act));
-                Stage* pr = (si + 1 < (int)n->st.size() && n->st[si + 1].kind == ST_PRELU) ? &n->st[si + 1] : nullptr;
+                Stage* pr = (has_next && n->st[si + 1].kind == ST_PRELU) ? &n->st[si + 1] : nullptr;
                 if (pr) {
                     const bool dm = pr->mask_kind == 2 && train;
                     act.slope = P + pr->slope_off;
@@ -405,7 +438,7 @@ static int forward_run(fg_net* n, long long* out_offset) {
                                          (train && s.x6_off >= 0) ? (void*)(ws + s.x6_off) : nullptr, &s.x6_valid,
                                          bn ? ws + bn->stats_off : nullptr, bn ? bn->stats_cap : 0, bn ? &bn->stats_rows : nullptr,
                                          pr ? &act : nullptr,
-                                         (si + 1 < (int)n->st.size() && n->st[si + 1].kind == ST_ACTPOOL && fg_fuse_prelu(ctx)) ? &n->pend : nullptr);
+                                         (has_next && n->st[si + 1].kind == ST_ACTPOOL && fg_fuse_prelu(ctx)) ? &n->pend : nullptr);
                 if (pr && !rc) pr->act_done = act.applied;
                 break;
             }
@@ -415,7 +448,7 @@ static int forward_run(fg_net* n, long long* out_offset) {
             case ST_THIN_IN: {
                 // a plain PReLU directly behind rides on the MFMA kernel's epilogue
                 FgActFuse act; memset(&act, 0, sizeof(act));
-                Stage* pr = (si + 1 < (int)n->st.size() && n->st[si + 1].kind == ST_PRELU && n->st[si + 1].mask_kind == 0)
+                Stage* pr = (has_next && n->st[si + 1].kind == ST_PRELU && n->st[si + 1].mask_kind == 0)
                                 ? &n->st[si + 1] : nullptr;
                 if (pr) {
                     act.slope = P + pr->slope_off; act.mscale = 1.f; pr->act_done = 0;
@@ -489,6 +522,13 @@ static int forward_run(fg_net* n, long long* out_offset) {
                 rc = fg_launch_mul_mask(ctx, cur, train ? mask : nullptr, train ? 1.f / (1.f - s.p) : 1.f, y,
                                         (long long)B * s.ic * s.ih * s.iw);
                 break;
+            case ST_JOIN: {
+                FgRowParts a; memset(&a, 0, sizeof(a));
+                a.n = n->n_branch;
+                for (int k = 0; k < a.n; ++k) { a.p[k] = ws + n->st[n->br_last[k]].out_off; a.w[k] = n->br_w[k]; }
+                rc = fg_launch_join_rows(ctx, a, y, B);
+                break;
+            }
             default: rc = fg_set_err(ctx, FG_ERR_INVALID, "fg_net_forward: bad stage kind %d", s.kind);
         }
         if (rc) return rc;
@@ -517,11 +557,56 @@ int fg_net_create(fg_ctx* ctx, const fg_layer_spec* L, int nl, int in_c, int in_
     auto fail = [&](int code, const char* msg, int i) {
         rc = fg_set_err(ctx, code, "fg_net_create: layer %d: %s", i, msg);
     };
+    // nn.ConcatTable markers (FG_CONCAT_TABLE / FG_BRANCH / FG_JOIN_TABLE, include/facegen_hip.h)
+    int tbl_n = 0, tbl_seen = 0;          // branches announced / started
+    bool tbl_open = false, tbl_done = false, head_pending = false;
+    size_t br_first = 0;                  // n->st.size() when the current branch started
+    auto close_branch = [&](int i) {      // the branch in front of marker i must have left a per-sample feature vector
+        if (n->st.size() == br_first) return fail(FG_ERR_INVALID, "empty nn.ConcatTable branch in front of this marker", i);
+        if (h * w > 1 || perm_hw > 1)
+            return fail(FG_ERR_UNSUPPORTED, "the nn.ConcatTable branch in front of this marker ends in a spatial map, not in a feature vector (nn.Linear)", i);
+        n->st.back().branch_end = tbl_seen - 1;
+        n->br_last[tbl_seen - 1] = (int)n->st.size() - 1; n->br_w[tbl_seen - 1] = c;
+    };
     for (int i = 0; i < nl && rc == FG_OK;) {
         Stage s; s.first_layer = i; s.ic = c; s.ih = h; s.iw = w;
         const fg_layer_spec& l = L[i];
         int consumed = 1;
+        bool marker = false;
+        if (tbl_open && tbl_seen == 0 && l.type != FG_BRANCH && l.type != FG_CONCAT_TABLE) { fail(FG_ERR_INVALID, "FG_BRANCH must follow FG_CONCAT_TABLE", i); break; }
+        if (tbl_open && l.type == FG_BATCHNORM) { fail(FG_ERR_UNSUPPORTED, "SpatialBatchNormalization inside an nn.ConcatTable branch", i); break; }
         switch (l.type) {
+            case FG_CONCAT_TABLE: {
+                marker = true;
+                if (tbl_open) { fail(FG_ERR_UNSUPPORTED, "nested nn.ConcatTable", i); break; }
+                if (tbl_done) { fail(FG_ERR_UNSUPPORTED, "a second nn.ConcatTable", i); break; }
+                if (i != 0) { fail(FG_ERR_UNSUPPORTED, "nn.ConcatTable must be the net's first layer", i); break; }
+                if (l.a < 2 || l.a > FG_TABLE_MAX) { fail(FG_ERR_UNSUPPORTED, "nn.ConcatTable: 2 to 4 branches", i); break; }
+                tbl_open = true; tbl_n = l.a; tbl_seen = 0;
+                break;
+            }
+            case FG_BRANCH: {
+                marker = true;
+                if (!tbl_open) { fail(FG_ERR_INVALID, "FG_BRANCH without FG_CONCAT_TABLE", i); break; }
+                if (tbl_seen > 0) { close_branch(i); if (rc != FG_OK) break; }
+                if (tbl_seen == tbl_n) { fail(FG_ERR_INVALID, "more FG_BRANCH markers than FG_CONCAT_TABLE announced", i); break; }
+                ++tbl_seen; br_first = n->st.size(); head_pending = true;
+                c = in_c; h = in_h; w = in_w; perm_c = perm_hw = 0;
+                break;
+            }
+            case FG_JOIN_TABLE: {
+                marker = true;
+                if (!tbl_open) { fail(FG_ERR_INVALID, "FG_JOIN_TABLE without FG_CONCAT_TABLE", i); break; }
+                close_branch(i); if (rc != FG_OK) break;
+                if (tbl_seen != tbl_n) { fail(FG_ERR_INVALID, "FG_JOIN_TABLE: fewer FG_BRANCH markers than FG_CONCAT_TABLE announced", i); break; }
+                tbl_open = false; tbl_done = true; n->n_branch = tbl_n;
+                s.kind = ST_JOIN; s.src = -2; s.last_layer = i;
+                s.ic = 0; for (int k = 0; k < tbl_n; ++k) s.ic += n->br_w[k];
+                s.ih = s.iw = 1; s.oc = s.ic; s.oh = s.ow = 1;
+                c = s.oc; h = w = 1;
+                n->st.push_back(s);
+                break;
+            }
             case FG_LINEAR: {
                 if (h != 1 || w != 1 || l.a != c) { fail(FG_ERR_INVALID, "Linear input size mismatch", i); break; }
                 s.w_off = poff; s.w_n = (long long)l.a * l.b; s.b_off = poff + s.w_n; s.b_n = l.b;
@@ -655,7 +740,10 @@ int fg_net_create(fg_ctx* ctx, const fg_layer_spec* L, int nl, int in_c, int in_
             default: fail(FG_ERR_INVALID, "unknown layer type", i); break;
         }
         if (rc != FG_OK) break;
+        if (marker) { ++i; continue; }         // markers own no stage a layer index could name (the join stage belongs to none)
         s.last_layer = i + consumed - 1;
+        s.src = head_pending ? -1 : (int)n->st.size() - 1;
+        if (s.kind != 0 && head_pending) { s.head_of = tbl_seen - 1; head_pending = false; }
         if (s.kind != 0) {
             for (int j = i; j <= s.last_layer; ++j) n->layers[j].stage = (int)n->st.size();
             n->layers[s.last_layer].ends_stage = 1;
@@ -672,17 +760,18 @@ int fg_net_create(fg_ctx* ctx, const fg_layer_spec* L, int nl, int in_c, int in_
                 review_factor = 0;
                 if (s.has_sigmoid) { rc = fg_set_err(ctx, FG_ERR_UNSUPPORTED, "fg_net_create: layer %d: Sigmoid fused in front of the view", i); break; }
                 Stage v; v.kind = ST_REVIEW; v.first_layer = v.last_layer = i; v.factor = f;
-                v.ic = c; v.ih = h; v.iw = w; v.oc = c / (f * f); v.oh = h * f; v.ow = w * f;
+                v.ic = c; v.ih = h; v.iw = w; v.oc = c / (f * f); v.oh = h * f; v.ow = w * f; v.src = (int)n->st.size() - 1;
                 n->layers[i].stage = (int)n->st.size();
                 c = v.oc; h = v.oh; w = v.ow;
                 n->st.push_back(v);
             }
-        } else if (!n->st.empty()) {
+        } else if (n->st.size() > br_first) {
             n->layers[i].stage = (int)n->st.size() - 1;
             n->layers[i].ends_stage = 1;
         }
         i += consumed;
     }
+    if (rc == FG_OK && tbl_open) rc = fg_set_err(ctx, FG_ERR_INVALID, "fg_net_create: layer %d: FG_CONCAT_TABLE is never closed by FG_JOIN_TABLE", 0);
     if (rc == FG_OK && n->st.empty()) rc = fg_set_err(ctx, FG_ERR_INVALID, "fg_net_create: no compute stages");
     n->n_params = poff; n->n_buffers = boff;
     // packed-weight storage (owned by the net; allocated here, never on the hot path).  The contraction stages share one

@@ -1435,6 +1435,78 @@ int fg_launch_add(fg_ctx* ctx, const float* a, const float* b, float* out, long 
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }
+// nn.ConcatTable / nn.JoinTable(2) inside ONE compiled net (FG_CONCAT_TABLE .. FG_JOIN_TABLE, models.lua:305-312): the n-way join of the
+// branches' per-sample feature vectors, its split for the backward pass and the sum of the branches' input gradients.  One block row
+// per sample (blockIdx.y), one thread per float4 (V = 4: every width a multiple of 4, every pointer 16-byte aligned) or per float of
+// the JOINED row; the branch a column belongs to is found by at most three compares: 32-bit indices, no division.
+template <int V, bool SPLIT>
+__global__ __launch_bounds__(256) void rows_join_split_kernel(FgRowParts a, float* __restrict__ joined, int rows, int W) {
+    const int col = (blockIdx.x * 256 + threadIdx.x) * V;
+    if (col >= W) return;
+    int k = 0, off = 0;
+#pragma unroll
+    for (int i = 0; i + 1 < FG_TABLE_MAX; ++i)
+        if (i + 1 < a.n && col >= off + a.w[k]) { off += a.w[k]; ++k; }
+    float* part = a.p[k];
+    if (!part) return;               // split: a branch nobody asked for
+    const int wk = a.w[k], j = col - off;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
+        float* pj = joined + r * W + col;
+        float* pp = part + r * wk + j;
+        if (V == 4) { if (SPLIT) *(float4*)pp = *(const float4*)pj; else *(float4*)pj = *(const float4*)pp; }
+        else { if (SPLIT) *pp = *pj; else *pj = *pp; }
+    }
+}
+static int launch_rows(fg_ctx* ctx, const FgRowParts& a, float* joined, int rows, bool split) {
+    long long W = 0;
+    bool v4 = ((size_t)joined & 15) == 0;
+    if (a.n < 1 || a.n > FG_TABLE_MAX) return fg_set_err(ctx, FG_ERR_INVALID, "join / split: 1 to %d parts", FG_TABLE_MAX);
+    for (int i = 0; i < a.n; ++i) {
+        if (a.w[i] <= 0) return fg_set_err(ctx, FG_ERR_INVALID, "join / split: width of part %d", i);
+        W += a.w[i];
+        v4 = v4 && a.w[i] % 4 == 0 && ((size_t)a.p[i] & 15) == 0;
+    }
+    if (rows <= 0) return FG_OK;
+    if (W * rows >= (1LL << 31)) return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "join / split: more than 2^31 elements");
+    const dim3 grid(fg_cdiv(W, v4 ? 1024 : 256), rows < 32768 ? rows : 32768);
+    if (v4 && split) hipLaunchKernelGGL((rows_join_split_kernel<4, true>), grid, dim3(256), 0, ctx->stream, a, joined, rows, (int)W);
+    else if (v4) hipLaunchKernelGGL((rows_join_split_kernel<4, false>), grid, dim3(256), 0, ctx->stream, a, joined, rows, (int)W);
+    else if (split) hipLaunchKernelGGL((rows_join_split_kernel<1, true>), grid, dim3(256), 0, ctx->stream, a, joined, rows, (int)W);
+    else hipLaunchKernelGGL((rows_join_split_kernel<1, false>), grid, dim3(256), 0, ctx->stream, a, joined, rows, (int)W);
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
+int fg_launch_join_rows(fg_ctx* ctx, const FgRowParts& a, float* out, int rows) { return launch_rows(ctx, a, out, rows, false); }
+int fg_launch_split_rows(fg_ctx* ctx, const float* g, const FgRowParts& a, int rows) { return launch_rows(ctx, a, (float*)g, rows, true); }
+// out = ((p0 + p1) + p2) + p3, in that order (nn.ConcatTable:updateGradInput; a fixed order keeps replicas identical across ranks)
+template <int V>
+__global__ __launch_bounds__(256) void sum_parts_kernel(FgRowParts a, float* __restrict__ out, long long n) {
+    const long long step = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
+        if (V == 4) {
+            float4 s = ((const float4*)a.p[0])[i];
+#pragma unroll
+            for (int k = 1; k < FG_TABLE_MAX; ++k)
+                if (k < a.n) { const float4 t = ((const float4*)a.p[k])[i]; s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w; }
+            ((float4*)out)[i] = s;
+        } else {
+            float s = a.p[0][i];
+#pragma unroll
+            for (int k = 1; k < FG_TABLE_MAX; ++k) if (k < a.n) s += a.p[k][i];
+            out[i] = s;
+        }
+    }
+}
+int fg_launch_sum_parts(fg_ctx* ctx, const FgRowParts& a, float* out, long long n) {
+    if (a.n < 1 || a.n > FG_TABLE_MAX) return fg_set_err(ctx, FG_ERR_INVALID, "sum: 1 to %d parts", FG_TABLE_MAX);
+    if (n <= 0) return FG_OK;
+    bool v4 = n % 4 == 0 && ((size_t)out & 15) == 0;
+    for (int i = 0; i < a.n; ++i) v4 = v4 && ((size_t)a.p[i] & 15) == 0;
+    if (v4) hipLaunchKernelGGL((sum_parts_kernel<4>), FG_GRID(n / 4, 256), dim3(256), 0, ctx->stream, a, out, n / 4);
+    else hipLaunchKernelGGL((sum_parts_kernel<1>), FG_GRID(n, 256), dim3(256), 0, ctx->stream, a, out, n);
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
 // plain device copy (hipMemcpyAsync's blit kernel took ~0.4 ms for a 3 MB batch half on this stack: a 7 % tax on the c2f step)
 __global__ __launch_bounds__(256) void copy_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n) {
     const long long n4 = n >> 2;

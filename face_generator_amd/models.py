@@ -124,6 +124,90 @@ def create_D16_d(dimensions):
     return model
 
 
+def _seq(mods, dimensions):
+    s = nn.Sequential()
+    for m in mods:
+        s.add(m)
+    s.input_dims = tuple(dimensions)
+    return s
+
+
+def _conv(i, o, k, stride=1):
+    return nn.SpatialConvolution(i, o, k, k, stride, stride, (k - 1) // 2)
+
+
+def _dense_branch(inputSz, dimensions):
+    """The dense branch every three-branch discriminator shares (models.lua:138-144, 192-198, 250-256, 352-358)."""
+    return _seq([nn.View(inputSz), nn.Linear(inputSz, 1024), nn.PReLU(), nn.Dropout(), nn.Linear(1024, 1024), nn.PReLU()], dimensions)
+
+
+def _table_D(branches, joined, dimensions):
+    """ConcatTable{branches} -> JoinTable(2) -> Linear(joined, 1024) -> PReLU -> Dropout -> Linear(1024, 1) -> Sigmoid
+    (models.lua:146-160, 200-214, 258-272, 360-374)."""
+    tail = _seq([nn.Linear(joined, 1024), nn.PReLU(), nn.Dropout(), nn.Linear(1024, 1), nn.Sigmoid()], (joined, 1, 1))
+    model = nn.ConcatSequential(branches, tail)
+    model.input_dims = tuple(dimensions)
+    return model
+
+
+def create_D16(dimensions):
+    """models.lua:110-160 create_D16: ConcatTable{fine 3x3 branch, coarse 5x5 branch, dense branch}, each conv branch
+    conv-PReLU-conv-PReLU-MaxPool(2,2)-SpatialDropout(0.5)-View-Linear(.., 1024)-PReLU-Dropout(0.5)."""
+    c, h, w = dimensions
+    flat = 64 * h * w // 4
+    fine = _seq([_conv(c, 64, 3), nn.PReLU(), _conv(64, 64, 3), nn.PReLU(), nn.SpatialMaxPooling(2, 2), nn.SpatialDropout(),
+                 nn.View(flat), nn.Linear(flat, 1024), nn.PReLU(), nn.Dropout()], dimensions)
+    coarse = _seq([_conv(c, 32, 5), nn.PReLU(), _conv(32, 64, 5), nn.PReLU(), nn.SpatialMaxPooling(2, 2), nn.SpatialDropout(),
+                   nn.View(flat), nn.Linear(flat, 1024), nn.PReLU(), nn.Dropout()], dimensions)
+    return _table_D([fine, coarse, _dense_branch(c * h * w, dimensions)], 1024 + 1024 + 1024, dimensions)
+
+
+def _strided_branch(c, k, widths_strides, flat, nout, dropout, dimensions):
+    mods, i = [], c
+    for o, stride in widths_strides:
+        mods += [_conv(i, o, k, stride), nn.PReLU()]
+        i = o
+    mods += [nn.SpatialDropout(), nn.View(flat), nn.Linear(flat, nout), nn.PReLU()]
+    if dropout:
+        mods.append(nn.Dropout())
+    return _seq(mods, dimensions)
+
+
+def create_D16_b(dimensions):
+    """models.lua:161-216 create_D16_b: a 3x3 and a 5x5 branch of convolutions c-64-64-128-128, the last with stride 2, then
+    SpatialDropout(0.5)-View-Linear(.., 512)-PReLU-Dropout(0.5); the dense branch; Linear(512 + 512 + 1024, 1024) behind the join."""
+    c, h, w = dimensions
+    flat = 128 * h * w // 4
+    ws = [(64, 1), (64, 1), (128, 1), (128, 2)]
+    return _table_D([_strided_branch(c, 3, ws, flat, 512, True, dimensions), _strided_branch(c, 5, ws, flat, 512, True, dimensions),
+                     _dense_branch(c * h * w, dimensions)], 512 + 512 + 1024, dimensions)
+
+
+def create_D16_c(dimensions):
+    """models.lua:218-274 create_D16_c: the branches of create_D16_b with a fifth convolution 128 -> 512 at stride 2, Linear(.., 1024)
+    and no Dropout at the end of the two conv branches."""
+    c, h, w = dimensions
+    flat = 512 * h * w // 16
+    ws = [(64, 1), (64, 1), (128, 1), (128, 2), (512, 2)]
+    return _table_D([_strided_branch(c, 3, ws, flat, 1024, False, dimensions), _strided_branch(c, 5, ws, flat, 1024, False, dimensions),
+                     _dense_branch(c * h * w, dimensions)], 1024 + 1024 + 1024, dimensions)
+
+
+def create_D32(dimensions):
+    """models.lua:322-376 create_D32.  The Lua function reads the globals IMG_DIMENSIONS / INPUT_SZ (train.lua:84-91) instead of its
+    argument; they are the image dimensions, taken from `dimensions` here.  Fine branch: 3x3 c-64-64, MaxPool(2,2),
+    SpatialDropout(0.5), Linear(.., 1024), PReLU.  Coarse branch: 5x5 c-32-32, MaxPool, 5x5 32-54-54, MaxPool, SpatialDropout(0.5),
+    Linear(.., 1024)-PReLU-Dropout(0.5)-Linear(1024, 1024)-PReLU."""
+    c, h, w = dimensions
+    flat_f, flat_c = 64 * h * w // 4, 54 * h * w // 16
+    fine = _seq([_conv(c, 64, 3), nn.PReLU(), _conv(64, 64, 3), nn.PReLU(), nn.SpatialMaxPooling(2, 2), nn.SpatialDropout(),
+                 nn.View(flat_f), nn.Linear(flat_f, 1024), nn.PReLU()], dimensions)
+    coarse = _seq([_conv(c, 32, 5), nn.PReLU(), _conv(32, 32, 5), nn.PReLU(), nn.SpatialMaxPooling(2, 2),
+                   _conv(32, 54, 5), nn.PReLU(), _conv(54, 54, 5), nn.PReLU(), nn.SpatialMaxPooling(2, 2), nn.SpatialDropout(),
+                   nn.View(flat_c), nn.Linear(flat_c, 1024), nn.PReLU(), nn.Dropout(), nn.Linear(1024, 1024), nn.PReLU()], dimensions)
+    return _table_D([fine, coarse, _dense_branch(c * h * w, dimensions)], 1024 + 1024 + 1024, dimensions)
+
+
 def create_D(dimensions):
     """models.lua:98-104."""
     if dimensions[1] == 16:

@@ -895,9 +895,11 @@ class BCECriterion:
 
 
 class ConcatSequential(Sequential):
-    """models.lua:279-316 create_D16_d: nn.Sequential{ConcatTable{branch...}, JoinTable(2), tail...}.  Every branch and
-    the tail is compiled to its own fg_net; they share ONE flat parameter / gradient vector in the reference's order
-    (branch 1, branch 2, ..., tail), so getParameters(), the optimizers and the all-reduce see a single net."""
+    """models.lua:110-376 create_D16 / _b / _c / _d, create_D32: nn.Sequential{ConcatTable{branch...}, JoinTable(2), tail...}.
+    :cuda() compiles the whole net to ONE fg_net (FG_CONCAT_TABLE / FG_BRANCH / FG_JOIN_TABLE markers in the flat layer list), so
+    the step-level entries (fg_step_D / fg_step_G) carry it like any chain; the flat parameter / gradient vector is in the
+    reference's order (branch 1, branch 2, ..., tail).  cuda(composite=True) keeps the older route -- every branch and the tail
+    compiled to its own fg_net on slices of one flat vector, walked from Python (runtime.CompositeDeviceNet, two branches only)."""
 
     def __init__(self, branches, tail):
         super().__init__()
@@ -947,8 +949,19 @@ class ConcatSequential(Sequential):
         for p in self._parts():
             p.zeroGradParameters()
 
-    def cuda(self, ctx=None, max_batch=32):
+    def layer_specs(self):
+        """The flat spec of include/facegen_hip.h: CONCAT_TABLE(n), then BRANCH + its layers per branch, JOIN_TABLE, the tail."""
+        specs = [("CONCAT_TABLE", len(self.branches))]
+        for b in self.branches:
+            specs.append(("BRANCH",))
+            specs.extend(b.layer_specs())
+        specs.append(("JOIN_TABLE",))
+        return specs + self.tail.layer_specs()
+
+    def cuda(self, ctx=None, max_batch=32, composite=False):
         from . import runtime
+        if not composite:
+            return Sequential.cuda(self, ctx, max_batch)
         if self.device_net is not None:
             return self
         ctx = ctx or runtime.get_context()

@@ -120,7 +120,7 @@ def _bn_modules(inner):
 
 def state_dict(net):
     inner = net._inner()
-    if isinstance(inner, nn.ConcatSequential):     # per-part layer specs: ConcatTable / JoinTable have no fg_layer_spec
+    if isinstance(inner, nn.ConcatSequential):     # per-part layer specs: the checkpoint layout predates the table markers of the flat spec and stays as it is
         layers = {"branches": [b.layer_specs() for b in inner.branches], "tail": inner.tail.layer_specs()}
     else:
         layers = inner.layer_specs()

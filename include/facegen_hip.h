@@ -160,7 +160,25 @@ enum fg_layer_type {
     FG_DROPOUT = 9,         /* nn.Dropout(p) (v2) */
     FG_SIGMOID = 10,        /* nn.Sigmoid */
     FG_LEAKYRELU = 11,      /* LeakyReLU.lua, p = negative slope */
-    FG_MAXPOOL2 = 12        /* nn.SpatialMaxPooling(2,2) (models_c2f.lua:251, 256) */
+    FG_MAXPOOL2 = 12,       /* nn.SpatialMaxPooling(2,2) (models_c2f.lua:251, 256) */
+    /* nn.ConcatTable{nn.Sequential, ...} -> nn.JoinTable(2) (models.lua:110-316, 322-376: the discriminators create_D16*, create_D32)
+     * as markers inside the flat spec list:
+     *   FG_CONCAT_TABLE(a = n)  FG_BRANCH  <layers of branch 1>  FG_BRANCH  <layers of branch 2> ...  FG_JOIN_TABLE  <tail layers>
+     * Every branch sees the net's input; FG_JOIN_TABLE lays the branches' per-sample feature vectors side by side in branch order
+     * and the layers behind it read that row.  The markers count as layers for every `layer_index` (fg_net_param_offset reports no
+     * parameters for them, fg_net_layer_output is refused for them).  The flat parameter / gradient vector is in the reference's
+     * order -- branch 1, branch 2, ..., tail (Module:parameters()) -- and the dropout masks are numbered in module order, branches
+     * first.  The gradient wrt the input is the SUM of the branches' input gradients, added in the fixed order
+     * ((branch 1 + branch 2) + branch 3) + branch 4 (nn.ConcatTable:updateGradInput).
+     * Built: ONE table per net, as its first layer, not nested, 2 to 4 branches, every branch ending in a per-sample feature
+     * vector (nn.Linear [+ PReLU [+ Dropout]]), no SpatialBatchNormalization inside a branch.  Anything else is refused by
+     * fg_net_create (FG_ERR_UNSUPPORTED / FG_ERR_INVALID, the message names the layer).
+     * fg_net_backward_range / fg_net_stage_params and fg_gan_set_comm(..., overlap = 2) work on such a net like on a chain: the
+     * stages are [branch 1][branch 2]...[join][tail], the reverse walk splits the gradient at the join stage (which owns no
+     * parameters) and sums the input gradients behind stage 0. */
+    FG_CONCAT_TABLE = 13,   /* nn.ConcatTable with a = number of branches */
+    FG_BRANCH = 14,         /* the next branch (an nn.Sequential) starts; appears `a` times */
+    FG_JOIN_TABLE = 15      /* nn.JoinTable(2): closes the table */
 };
 typedef struct fg_layer_spec {
     int type;
@@ -411,6 +429,13 @@ int fg_dropout_apply(fg_ctx* ctx, const float* x, const float* mask, float scale
 int fg_concat_channels(fg_ctx* ctx, const float* a, const float* b, float* out, long long npix, int ca, int cb);
 int fg_split_channels(fg_ctx* ctx, const float* g, float* ga, float* gb, long long npix, int ca, int cb);
 int fg_add(fg_ctx* ctx, const float* a, const float* b, float* out, long long n);
+/* The n-way forms a compiled nn.ConcatTable net uses (1 <= n <= 4; `parts` / `widths`: HOST arrays of n device pointers / row widths):
+ * fg_join_rows: out[r][off_k + j] = parts[k][r][j] with off_k = widths[0] + ... + widths[k-1] (nn.JoinTable(2) on [rows][width] tensors);
+ * fg_split_rows: the reverse, parts[k] = NULL skips that part; fg_sum_n: out = ((parts[0] + parts[1]) + parts[2]) + parts[3], fp32
+ * additions in exactly that order.  16-byte accesses when every width is a multiple of 4 and every pointer 16-byte aligned. */
+int fg_join_rows(fg_ctx* ctx, const float* const* parts, const int* widths, int n, float* out, int rows);
+int fg_split_rows(fg_ctx* ctx, const float* g, float* const* parts, const int* widths, int n, int rows);
+int fg_sum_n(fg_ctx* ctx, const float* const* parts, int n, float* out, long long count);
 int fg_sigmoid_forward(fg_ctx* ctx, const float* x, float* y, long long n);
 int fg_sigmoid_backward(fg_ctx* ctx, const float* y, const float* gy, float* gx, long long n);
 int fg_leakyrelu_forward(fg_ctx* ctx, const float* x, float negslope, float* y, long long n);

@@ -57,7 +57,7 @@ int fg_nhwc_to_nchw(fg_ctx* ctx, const float* src, float* dst, int n, int c, int
 int fg_rng_uniform(fg_ctx* ctx, uint64_t seed, uint64_t offset, float* out, long long n, float lo, float hi);
 int fg_rng_bernoulli(fg_ctx* ctx, uint64_t seed, uint64_t offset, float* out, long long n, float keep_prob);
 int fg_rng_normal(fg_ctx* ctx, uint64_t seed, uint64_t offset, float* out, long long n, float mean, float std);
-enum fg_layer_type { FG_LINEAR = 1, FG_VIEW = 2, FG_PRELU = 3, FG_UPSAMPLE2X = 4, FG_CONV = 5, FG_BATCHNORM = 6, FG_SPATIAL_DROPOUT = 7, FG_AVGPOOL2 = 8, FG_DROPOUT = 9, FG_SIGMOID = 10, FG_LEAKYRELU = 11, FG_MAXPOOL2 = 12 };
+enum fg_layer_type { FG_LINEAR = 1, FG_VIEW = 2, FG_PRELU = 3, FG_UPSAMPLE2X = 4, FG_CONV = 5, FG_BATCHNORM = 6, FG_SPATIAL_DROPOUT = 7, FG_AVGPOOL2 = 8, FG_DROPOUT = 9, FG_SIGMOID = 10, FG_LEAKYRELU = 11, FG_MAXPOOL2 = 12, FG_CONCAT_TABLE = 13, FG_BRANCH = 14, FG_JOIN_TABLE = 15 };
 typedef struct fg_layer_spec { int type; int a, b, c, d; float p, q; } fg_layer_spec;
 int fg_net_create(fg_ctx* ctx, const fg_layer_spec* layers, int n_layers, int in_c, int in_h, int in_w, fg_net** out);
 int fg_net_destroy(fg_net* net);
@@ -159,6 +159,9 @@ int fg_dropout_apply(fg_ctx* ctx, const float* x, const float* mask, float scale
 int fg_concat_channels(fg_ctx* ctx, const float* a, const float* b, float* out, long long npix, int ca, int cb);
 int fg_split_channels(fg_ctx* ctx, const float* g, float* ga, float* gb, long long npix, int ca, int cb);
 int fg_add(fg_ctx* ctx, const float* a, const float* b, float* out, long long n);
+int fg_join_rows(fg_ctx* ctx, const float* const* parts, const int* widths, int n, float* out, int rows);
+int fg_split_rows(fg_ctx* ctx, const float* g, float* const* parts, const int* widths, int n, int rows);
+int fg_sum_n(fg_ctx* ctx, const float* const* parts, int n, float* out, long long count);
 int fg_sigmoid_forward(fg_ctx* ctx, const float* x, float* y, long long n);
 int fg_sigmoid_backward(fg_ctx* ctx, const float* y, const float* gy, float* gx, long long n);
 int fg_leakyrelu_forward(fg_ctx* ctx, const float* x, float negslope, float* y, long long n);
@@ -287,21 +290,48 @@ local function spec_of(m)
     end
     error('facegen_hip: module ' .. tostring(tn) .. ' is not on the hot path')
 end
+-- nn.Sequential -> the flat list of fg_layer_spec rows and the leaf modules in Module:parameters() order.  A chain maps one module
+-- to one row.  nn.Sequential{nn.ConcatTable{nn.Sequential, ...}, nn.JoinTable(2), tail...} (models.lua:110-316, the create_D16*
+-- discriminators) becomes FG_CONCAT_TABLE(n), FG_BRANCH + the rows of every branch, FG_JOIN_TABLE, the tail's rows: one fg_net.
+local function flatten(seq)
+    local specs, leaves = {}, {}
+    local function add_chain(mods, from)
+        for i = from, #mods do
+            specs[#specs + 1] = spec_of(mods[i]); leaves[#leaves + 1] = mods[i]
+        end
+    end
+    local first = seq.modules[1]
+    if torch.typename(first) == 'nn.ConcatTable' then
+        assert(torch.typename(seq.modules[2]) == 'nn.JoinTable' and seq.modules[2].dimension == 2,
+               'facegen_hip: nn.ConcatTable must be followed by nn.JoinTable(2)')
+        specs[#specs + 1] = {C.FG_CONCAT_TABLE, #first.modules}
+        for _, branch in ipairs(first.modules) do
+            assert(torch.typename(branch) == 'nn.Sequential', 'facegen_hip: the branches of an nn.ConcatTable must be nn.Sequential')
+            specs[#specs + 1] = {C.FG_BRANCH}
+            add_chain(branch.modules, 1)
+        end
+        specs[#specs + 1] = {C.FG_JOIN_TABLE}
+        add_chain(seq.modules, 3)
+    else
+        add_chain(seq.modules, 1)
+    end
+    return specs, leaves
+end
 
 -- DeviceNet: what `net:cuda()` becomes inside NN_UTILS.activateCuda (nn_utils.lua:328-363) --------------------------------
 local DeviceNet = {}
 DeviceNet.__index = DeviceNet
 function M.compile(seq, in_c, in_h, in_w, max_batch)
-    local n = #seq.modules
+    local rows, leaves = flatten(seq)
+    local n = #rows
     local specs = ffi.new('fg_layer_spec[?]', n)
-    for i, m in ipairs(seq.modules) do
-        local s = spec_of(m)
+    for i, s in ipairs(rows) do
         specs[i - 1].type = s[1]; specs[i - 1].a = s[2] or 0; specs[i - 1].b = s[3] or 0
         specs[i - 1].c = s[4] or 0; specs[i - 1].d = s[5] or 0; specs[i - 1].p = s[6] or 0; specs[i - 1].q = s[7] or 0
     end
     local out = ffi.new('fg_net*[1]')
     check(C.fg_net_create(ctx, specs, n, in_c, in_h, in_w, out))
-    local net = setmetatable({h = out[0], seq = seq, in_dims = {in_c, in_h, in_w}, max_batch = max_batch, train = true}, DeviceNet)
+    local net = setmetatable({h = out[0], seq = seq, leaves = leaves, in_dims = {in_c, in_h, in_w}, max_batch = max_batch, train = true}, DeviceNet)
     net.nparams = tonumber(C.fg_net_num_params(net.h))
     net.nbuffers = tonumber(C.fg_net_num_buffers(net.h))
     net.nmasks = C.fg_net_num_masks(net.h)
@@ -321,7 +351,7 @@ end
 function DeviceNet:upload()
     local flat, off = torch.FloatTensor(self.nparams), 1
     local buf, boff = torch.FloatTensor(math.max(1, self.nbuffers)):zero(), 1
-    for _, m in ipairs(self.seq.modules) do
+    for _, m in ipairs(self.leaves) do
         for _, name in ipairs({'weight', 'bias'}) do
             if m[name] then
                 local k = m[name]:nElement()
@@ -343,7 +373,7 @@ end
 function DeviceNet:download(want_grads)
     local flat, gflat, off = self.params:float(), want_grads and self.grads:float() or nil, 1
     local buf, boff = self.nbuffers > 0 and self.buffers:float() or nil, 1
-    for _, m in ipairs(self.seq.modules) do
+    for _, m in ipairs(self.leaves) do
         for _, name in ipairs({'weight', 'bias'}) do
             if m[name] then
                 local k = m[name]:nElement()
