@@ -98,6 +98,10 @@ int fg_ctx_create(int device, fg_ctx** out) {
     if (const char* m = getenv("FG_WINO_WGRAD")) if (atoi(m) == 0) c->fusion &= ~FG_FUSE_WINOGRAD_WGRAD;
     c->fusion &= ~FG_FUSE_ADAM_PACK;        // measured slower than the two launches: opt-in
     if (const char* m = getenv("FG_ADAM_PACK")) if (atoi(m) != 0) c->fusion |= FG_FUSE_ADAM_PACK;
+    if (hipMalloc((void**)&c->grid_part, FG_GRID_PART_FLOATS * sizeof(float)) != hipSuccess) {
+        delete c;
+        return fg_set_err(nullptr, FG_ERR_NOMEM, "fg_ctx_create: hipMalloc");
+    }
     ++g_real_ctx;
     *out = c;
     return FG_OK;
@@ -107,6 +111,7 @@ int fg_ctx_destroy(fg_ctx* ctx) {
     if (ctx->device == FG_DEVICE_NONE) { if (--g_dry_ctx == 0) g_fg_dry = false; }
     else --g_real_ctx;
     if (ctx->clk_stream) { (void)hipStreamSynchronize(ctx->clk_stream); (void)hipStreamDestroy(ctx->clk_stream); (void)hipFree(ctx->clk_dev); }
+    if (ctx->grid_part) (void)hipFree(ctx->grid_part);
     delete ctx;
     return FG_OK;
 }

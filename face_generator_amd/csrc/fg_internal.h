@@ -7,6 +7,7 @@
 #include "../../include/facegen_hip.h"
 
 #define FG_THIN_WGRAD_BLOCKS 512   // max partial slabs of the thin weight-gradient kernel
+#define FG_GRID_PART_FLOATS 512
 #define FG_MAX_GROUPS 64   // (parity,tap) groups per launch table (7x7 plain = 49, folded dgrad = 36)
 
 #include <vector>
@@ -43,6 +44,7 @@ struct fg_ctx {
     // fg_prof_clock_*: a one-wave probe on its own stream (s_memtime against the 100 MHz s_memrealtime)
     hipStream_t clk_stream = nullptr;
     unsigned long long* clk_dev = nullptr;
+    float* grid_part = nullptr;      // fg_image_grid: the min / max partials between its two launches (FG_GRID_PART_FLOATS, sample.hip)
 };
 // true the first time `key` (the address of a call site's static) is seen on this context: hipFuncSetAttribute is per device, so
 // the "done" flag belongs to the context, not to a process-wide static (one host thread may drive several devices)

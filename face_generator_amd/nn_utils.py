@@ -46,6 +46,45 @@ def createImages(N, outputAsList=False, refineWithG=None):
     return createImagesFromNoise(createNoiseInputs(N), outputAsList, refineWithG)
 
 
+_SAMPLER = {}
+
+
+def sampler(max_images):
+    """The runtime.Sampler over S.MODEL_G / S.MODEL_D with chunk = OPT.batchSize, built once per (nets, chunk) and grown when a
+    larger N is asked for.  Its noise stream is S's: seed and running offset go in before, and come back after, every draw."""
+    from .runtime import Sampler
+    dnG, dnD = S.MODEL_G._inner().device_net, S.MODEL_D._inner().device_net
+    if dnG is None or dnD is None:
+        from ._lib import FgError
+        raise FgError("sampler: move MODEL_G / MODEL_D to the device first (NN_UTILS.activateCuda)")
+    key = (id(dnG), id(dnD), S.OPT["batchSize"])
+    sm = _SAMPLER.get("sampler")
+    if sm is None or _SAMPLER.get("key") != key or sm.max_images < max_images:
+        _SAMPLER.clear()
+        sm = Sampler(dnG.ctx, dnG, dnD, max_images, S.OPT["batchSize"])
+        _SAMPLER.update(sampler=sm, key=key)
+    return sm
+
+
+def sampleRanked(N, nbMaxOut=None):
+    """createImages(N) + sortImagesByPrediction(images, false, nbMaxOut) + sortImagesByPrediction(images, true, nbMaxOut)
+    (sample.lua:80-85) on the sampler level: one fg_sample call -- noise, G and D in chunks of OPT.batchSize in EVALUATE mode,
+    both rankings -- and one copy back.  -> (images [N,C,H,W], best, best_preds, worst, worst_preds), host tensors / lists like
+    the functions it stands in for; equal scores are ordered by index (the tie rule of fg_rank_scores)."""
+    sm = sampler(N)
+    sm.set_seed(S.noise_seed, S.noise_offset)
+    sm.sample(N)
+    S.noise_offset += (N * sm.noise_dim + 3) // 4
+    k = N if not nbMaxOut else min(N, nbMaxOut)
+    images = sm.ctx.to_nchw(sm.view("IMAGES")).cpu()
+    preds = sm.view("PREDS").cpu()
+    out = [images]
+    for what in ("ORDER_DESC", "ORDER_ASC"):
+        order = sm.view(what)[:k].cpu().tolist()
+        out += [[images[i] for i in order], [float(preds[i]) for i in order]]
+    return tuple(out)
+
+
 def sortImagesByPrediction(images, ascending=False, nbMaxOut=None):
     """nn_utils.lua:90-118 (forward-only D ranking; evaluate-mode semantics come from the caller)."""
     imgs = torch.stack(list(images)) if isinstance(images, (list, tuple)) else images

@@ -567,3 +567,116 @@ class FusedGan:
     def _after(self, B, Bg):
         # keep the DeviceNets' own bookkeeping in step (layer_output / a later stand-alone backward read it)
         self.dnD._batch, self.dnG._batch = B, Bg
+
+
+class Sampler:
+    """fg_sampler (include/facegen_hip.h, sampler level): sample.lua:80-89 / NN_UTILS.visualizeProgress on the device -- noise,
+    G in chunks, D in chunks, both rankings and the display grids without a host round trip.  The workspace is a torch tensor
+    owned here; view() returns slices of it (valid until the next call that writes that buffer)."""
+    BUF = dict(NOISE=0, IMAGES=1, PREDS=2, ORDER_DESC=3, ORDER_ASC=4)
+
+    def __init__(self, ctx, dnG, dnD, max_images, chunk):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.dnG, self.dnD = dnG, dnD
+        if not isinstance(dnG, DeviceNet) or not isinstance(dnD, DeviceNet):
+            raise FgError("Sampler: both nets must be compiled to one device plan (net.cuda())")
+        self.max_images, self.chunk = int(max_images), int(chunk)
+        dnG.reserve(self.chunk)
+        dnD.reserve(self.chunk)
+        nbytes = self.lib.fg_sampler_workspace_bytes(dnG.h, dnD.h, self.max_images)
+        self.ws = (torch.zeros if ctx.dry else torch.empty)((nbytes + 3) // 4 + 64, dtype=torch.float32, device=ctx.device)
+        base = self.ws.data_ptr()
+        self._skip = ((-base) % 256) // 4                       # 256-byte aligned start inside the tensor
+        h = ctypes.c_void_p()
+        ctx.check(self.lib.fg_sampler_create(ctx.h, dnG.h, dnD.h, self.max_images, self.chunk, base + 4 * self._skip,
+                                             nbytes, ctypes.byref(h)))
+        self.h = h
+        self._bound = None
+        self.noise_dim = dnG.in_c * dnG.in_h * dnG.in_w
+        self.dims = (dnD.in_c, dnD.in_h, dnD.in_w)
+        self.n = 0
+
+    def __del__(self):
+        try:
+            self.lib.fg_sampler_destroy(self.h)
+        except Exception:
+            pass
+
+    def _bind(self):
+        key = (self.dnG.ws.data_ptr(), self.dnG.ws.numel(), self.dnD.ws.data_ptr(), self.dnD.ws.numel())
+        if key != self._bound:
+            self.ctx.check(self.lib.fg_sampler_bind_workspaces(self.h, key[0], key[1] * 4, key[2], key[3] * 4))
+            self._bound = key
+
+    def set_seed(self, seed, offset=0):
+        self.ctx.check(self.lib.fg_sampler_set_seed(self.h, seed, offset))
+
+    def view(self, what, n=None):
+        """NOISE [n, noiseDim], IMAGES [n, H, W, C] (NHWC), PREDS [n], ORDER_DESC / ORDER_ASC int32 [n]; n defaults to the
+        count of the last generate / score / sample call."""
+        off, cnt = ctypes.c_longlong(), ctypes.c_longlong()
+        self.ctx.check(self.lib.fg_sampler_buffer(self.h, self.BUF[what], ctypes.byref(off), ctypes.byref(cnt)))
+        n = self.n if n is None else n
+        per = cnt.value // self.max_images
+        o = self._skip + off.value
+        t = self.ws[o: o + n * per]
+        if what == "NOISE":
+            return t.view(n, per)
+        if what == "IMAGES":
+            c, h, w = self.dims
+            return t.view(n, h, w, c)
+        if what == "PREDS":
+            return t
+        return t.view(torch.int32)
+
+    @staticmethod
+    def _p(t):
+        return t.data_ptr() if t is not None else None
+
+    def generate(self, n, noise=None):
+        self._bind()
+        keep = noise.contiguous() if noise is not None else None
+        self.ctx.check(self.lib.fg_sample_generate(self.h, int(n), self._p(keep)))
+        self.n = int(n)
+        return self.view("IMAGES")
+
+    def score(self, n=None, images=None):
+        """images: a device NHWC batch to score instead of the sampler's own (visualizeProgress plants two of its own)."""
+        self._bind()
+        n = self.n if n is None else int(n)
+        keep = images.contiguous() if images is not None else None
+        self.ctx.check(self.lib.fg_sample_score(self.h, n, self._p(keep)))
+        self.n = n
+        return self.view("PREDS")
+
+    def rank(self, ascending=False, n=None):
+        """fg_rank_scores on the sampler's own PREDS, into ORDER_ASC / ORDER_DESC."""
+        n = self.n if n is None else int(n)
+        out = self.view("ORDER_ASC" if ascending else "ORDER_DESC", n)
+        self.ctx.check(self.lib.fg_rank_scores(self.ctx.h, self.view("PREDS", n).data_ptr(), n, 1 if ascending else 0,
+                                               out.data_ptr(), None, 0))
+        return out
+
+    def sample(self, n, noise=None):
+        self._bind()
+        keep = noise.contiguous() if noise is not None else None
+        self.ctx.check(self.lib.fg_sample(self.h, int(n), self._p(keep)))
+        self.n = int(n)
+
+    def grid(self, order, k, nrow, padding=0, normalize=True, images=None):
+        """image.toDisplayTensor over the first k entries of `order` ("ORDER_DESC" / "ORDER_ASC", a device int32 tensor, or
+        None for 0..k-1) -> device CHW tensor (fg_image_grid)."""
+        if isinstance(order, str):
+            order = self.view(order)
+        if order is not None:
+            if order.dtype != torch.int32 or order.numel() < k:
+                raise FgError("Sampler.grid: order must hold at least k int32 indices")
+            order = order.contiguous()
+        imgs = self.view("IMAGES") if images is None else images.contiguous()
+        c, h, w = self.dims
+        xmaps = min(int(nrow), int(k))
+        ymaps = (k + xmaps - 1) // xmaps
+        out = self.ctx.empty(c, ymaps * (h + padding), xmaps * (w + padding))
+        self.ctx.check(self.lib.fg_image_grid(self.ctx.h, imgs.data_ptr(), self._p(order), int(k), c, h, w, int(nrow), int(padding),
+                                              1 if normalize else 0, out.data_ptr(), None))
+        return out

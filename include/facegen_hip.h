@@ -29,6 +29,7 @@ typedef struct fg_ctx fg_ctx;
 typedef struct fg_net fg_net;
 typedef struct fg_comm fg_comm;
 typedef struct fg_gan fg_gan;
+typedef struct fg_sampler fg_sampler;
 
 enum {
     FG_OK = 0,
@@ -351,6 +352,64 @@ int fg_step_G(fg_gan* gan, int batch, const float* cond, const float* noise, con
 int fg_gan_update(fg_gan* gan, int which);
 int fg_gan_finish_pending(fg_gan* gan);
 int fg_gan_pending(const fg_gan* gan);   /* 1 while D's update is deferred behind its gradient all-reduce */
+
+/* ---- sampler level: sample.lua:80-89 and NN_UTILS.visualizeProgress (nn_utils.lua:131-204) as device-resident entries ----
+ * Two module-level operations, usable alone, and one object built from them.
+ *
+ * fg_rank_scores = the sort of NN_UTILS.sortImagesByPrediction (nn_utils.lua:99-106): order_out[r] (device int[n]) is the 0-based
+ *   index of the score at rank r.  Lua's table.sort leaves the order of equal scores undefined and D's sigmoid saturates to exactly
+ *   1.0f, so the order is FIXED here: descending = (score high -> low, index low -> high), ascending = (score low -> high, index
+ *   low -> high); -0.0f ties with +0.0f; NaN scores come last in both directions, lowest index first.  No atomics: the result does
+ *   not depend on scheduling.  1 <= n <= 1048576 (larger: FG_ERR_UNSUPPORTED, the message names n).  This implementation counts
+ *   ranks instead of sorting and needs no scratch: fg_rank_scores_workspace_bytes is 0 and `scratch` may be NULL (the pair stays in
+ *   the signature so that a sorting implementation can take its place).
+ *
+ * fg_image_grid = image.toDisplayTensor{input = images, nrow = nrow, padding = padding} of the Torch7 `image` package over the k
+ *   images order[0..k-1] (order == NULL: 0..k-1) of images_nhwc [*][h][w][c].  The package is an un-vendored luarocks dependency
+ *   of the reference, so this is a restatement of its documented behaviour -- PARITY UNPINNED, like fg_scale_bilinear:
+ *   xmaps = min(nrow, k), ymaps = ceil(k / xmaps); grid_chw is [c][ymaps * (h + padding)][xmaps * (w + padding)] (CHW, what
+ *   image.save takes); image j sits in cell (j / xmaps, j % xmaps) at offset padding / 2 (integer division) from the cell's corner;
+ *   every element no image covers holds the maximum over the k selected images.  normalize = 1 maps the whole grid by
+ *   (v - min) / (max - min), min / max over the k selected images (max == min: all 0); normalize = 0 keeps raw values.
+ *   minmax_out: device float[2] = {min, max}, or NULL.  The reduction runs in a fixed order.
+ *
+ * fg_sampler: G and D are fg_net objects bound to their vectors; neither may be a table-input net (the c2f pair of fg_gan's
+ *   table_inputs = 1 is refused, FG_ERR_UNSUPPORTED).  D may be any net that compiles to one plan, nn.ConcatTable ones included.
+ *   ws: fg_sampler_workspace_bytes, 256-byte aligned; the nets' own workspaces hold `chunk` samples each
+ *   (fg_sampler_bind_workspaces checks fg_net_workspace_bytes(net, chunk)).  Both nets run in EVALUATE mode (running BatchNorm
+ *   statistics, dropout off): nothing they own changes.  Every entry stays on the context's stream and never synchronises.
+ *   fg_sample_generate = createNoiseInputs + createImagesFromNoise (nn_utils.lua:35-69): noise == NULL draws n vectors with one
+ *     Philox launch -- exactly fg_rng_uniform(seed, offset, n * noiseDim, -1, 1), the offset then advances by ceil(n * noiseDim / 4)
+ *     -- else noise is a device [n][noiseDim] (16-byte aligned); G runs over chunks of `chunk` and a tail of n % chunk, each
+ *     straight into its slice of FG_SAMPLER_IMAGES (NHWC [n][H][W][C]).
+ *   fg_sample_score = the prediction loop of sortImagesByPrediction (nn_utils.lua:91-97) over the same chunks into
+ *     FG_SAMPLER_PREDS; images != NULL scores a caller's device batch [n][H][W][C] instead (visualizeProgress plants a real face
+ *     and a non-face among the samples).
+ *   fg_sample = generate + score + both rankings (sample.lua:80-85): D runs ONCE per image -- the reference scores all images
+ *     again for "worst", which in evaluate mode recomputes the same numbers -- and FG_SAMPLER_ORDER_DESC / _ASC hold both orders.
+ *   chunk: the chunk's noise and image slices must start on 16 bytes (chunk * noiseDim and chunk * H * W * C multiples of 4; else
+ *     fg_sampler_create refuses the chunk); a chunk that is not a multiple of 4 costs one small copy per chunk into PREDS. */
+enum fg_sampler_buffer_id {
+    FG_SAMPLER_NOISE = 0,       /* [max_images][noiseDim]: the noise the last fg_sample_generate drew                    */
+    FG_SAMPLER_IMAGES = 1,      /* [max_images][H][W][C]                                                                 */
+    FG_SAMPLER_PREDS = 2,       /* [max_images] D's probabilities                                                        */
+    FG_SAMPLER_ORDER_DESC = 3,  /* int[max_images] (same storage as floats): best first                                  */
+    FG_SAMPLER_ORDER_ASC = 4    /* int[max_images]: worst first                                                          */
+};
+size_t fg_rank_scores_workspace_bytes(int n);
+int fg_rank_scores(fg_ctx* ctx, const float* scores, int n, int ascending, int* order_out, void* scratch, size_t scratch_bytes);
+int fg_image_grid(fg_ctx* ctx, const float* images_nhwc, const int* order, int k, int c, int h, int w, int nrow, int padding,
+                  int normalize, float* grid_chw, float* minmax_out);
+size_t fg_sampler_workspace_bytes(const fg_net* G, const fg_net* D, int max_images);
+int fg_sampler_create(fg_ctx* ctx, fg_net* G, fg_net* D, int max_images, int chunk, void* ws, size_t ws_bytes, fg_sampler** out);
+int fg_sampler_destroy(fg_sampler* s);
+int fg_sampler_bind_workspaces(fg_sampler* s, void* wsG, size_t wsG_bytes, void* wsD, size_t wsD_bytes);
+int fg_sampler_set_seed(fg_sampler* s, uint64_t seed, uint64_t offset);
+/* offset (in floats, relative to the sampler workspace) and length of a buffer */
+int fg_sampler_buffer(const fg_sampler* s, int what, long long* offset_floats, long long* count);
+int fg_sample_generate(fg_sampler* s, int n, const float* noise);
+int fg_sample_score(fg_sampler* s, int n, const float* images);
+int fg_sample(fg_sampler* s, int n, const float* noise);
 
 /* ---- adversarial.approxParzen (adversarial_c2f.lua:305-344): dist[i] = || (gen[i] + cond) - fine ||_2 for the n
  *      generations of one example (torch.dist: squares accumulated in double), min_out[0] = min(1e10, min_i dist[i]).

@@ -27,6 +27,7 @@ typedef struct fg_ctx fg_ctx;
 typedef struct fg_net fg_net;
 typedef struct fg_comm fg_comm;
 typedef struct fg_gan fg_gan;
+typedef struct fg_sampler fg_sampler;
 enum { FG_OK = 0, FG_ERR_INVALID = -1, FG_ERR_HIP = -2, FG_ERR_NOMEM = -3, FG_ERR_UNSUPPORTED = -4, FG_ERR_WORKSPACE = -5 };
 int fg_set_math(fg_ctx* ctx, int mode);
 int fg_get_math(fg_ctx* ctx);
@@ -128,6 +129,19 @@ int fg_step_G(fg_gan* gan, int batch, const float* cond, const float* noise, con
 int fg_gan_update(fg_gan* gan, int which);
 int fg_gan_finish_pending(fg_gan* gan);
 int fg_gan_pending(const fg_gan* gan);
+enum fg_sampler_buffer_id { FG_SAMPLER_NOISE = 0, FG_SAMPLER_IMAGES = 1, FG_SAMPLER_PREDS = 2, FG_SAMPLER_ORDER_DESC = 3, FG_SAMPLER_ORDER_ASC = 4 };
+size_t fg_rank_scores_workspace_bytes(int n);
+int fg_rank_scores(fg_ctx* ctx, const float* scores, int n, int ascending, int* order_out, void* scratch, size_t scratch_bytes);
+int fg_image_grid(fg_ctx* ctx, const float* images_nhwc, const int* order, int k, int c, int h, int w, int nrow, int padding, int normalize, float* grid_chw, float* minmax_out);
+size_t fg_sampler_workspace_bytes(const fg_net* G, const fg_net* D, int max_images);
+int fg_sampler_create(fg_ctx* ctx, fg_net* G, fg_net* D, int max_images, int chunk, void* ws, size_t ws_bytes, fg_sampler** out);
+int fg_sampler_destroy(fg_sampler* s);
+int fg_sampler_bind_workspaces(fg_sampler* s, void* wsG, size_t wsG_bytes, void* wsD, size_t wsD_bytes);
+int fg_sampler_set_seed(fg_sampler* s, uint64_t seed, uint64_t offset);
+int fg_sampler_buffer(const fg_sampler* s, int what, long long* offset_floats, long long* count);
+int fg_sample_generate(fg_sampler* s, int n, const float* noise);
+int fg_sample_score(fg_sampler* s, int n, const float* images);
+int fg_sample(fg_sampler* s, int n, const float* noise);
 int fg_parzen_min_dist(fg_ctx* ctx, const float* gen, const float* cond, const float* fine, int n, long long elems, float* dist, float* min_out);
 int fg_scale_bilinear(fg_ctx* ctx, const float* src, float* dst, int n, int c, int hs, int ws, int hd, int wd, int layout);
 int fg_c2f_coarse_diff(fg_ctx* ctx, const float* fine, float* coarse, float* diff, float* tmp, int n, int c, int s, int cs, int layout);
@@ -658,5 +672,92 @@ function Gan:update(which)
     if which == 'D' then self.D:markDeviceNewer() else self.G:markDeviceNewer() end
 end
 function Gan:finishPending() check(C.fg_gan_finish_pending(self.h)) end
+
+-- (iii) sampler level: fg_sampler_* -- sample.lua:80-89 / NN_UTILS.visualizeProgress without a host round trip ---------------------
+local Sampler = {}
+Sampler.__index = Sampler
+function M.Sampler(dnG, dnD, max_images, chunk)
+    local bytes = tonumber(C.fg_sampler_workspace_bytes(dnG.h, dnD.h, max_images))
+    local ws = M.DeviceTensor(math.ceil(bytes / 4) + 64)
+    local base = ffi.cast('char*', ws.ptr)
+    local skip = (256 - tonumber(ffi.cast('uintptr_t', base) % 256)) % 256
+    local out = ffi.new('fg_sampler*[1]')
+    check(C.fg_sampler_create(ctx, dnG.h, dnD.h, max_images, chunk, base + skip, bytes, out))
+    local s = setmetatable({h = out[0], ws = ws, base = ffi.cast('float*', base + skip), G = dnG, D = dnD, max_images = max_images,
+                            chunk = chunk, n = 0, dims = dnD.in_dims}, Sampler)
+    check(C.fg_sampler_bind_workspaces(s.h, dnG.ws.ptr, dnG.ws_bytes, dnD.ws.ptr, dnD.ws_bytes))   -- each sized for >= chunk samples
+    check(C.fg_sampler_set_seed(s.h, M.seed, 0))
+    ffi.gc(s.h, C.fg_sampler_destroy)
+    return s
+end
+function Sampler:setSeed(seed, offset) check(C.fg_sampler_set_seed(self.h, seed, offset or 0)) end
+-- device pointer of a buffer (C.FG_SAMPLER_*) and its length in floats
+function Sampler:ptr(what)
+    local off, cnt = ffi.new('long long[1]'), ffi.new('long long[1]')
+    check(C.fg_sampler_buffer(self.h, what, off, cnt))
+    return self.base + off[0], tonumber(cnt[0])
+end
+-- the nets run in evaluate mode whatever their own flag says; what the trainer left on the device is what gets sampled
+function Sampler:sync()
+    if not self.G.device_newer then self.G:upload() end
+    if not self.D.device_newer then self.D:upload() end
+end
+function Sampler:generate(n, noise)           -- noise: DeviceTensor [n][noiseDim] or nil (drawn by the library)
+    self:sync()
+    check(C.fg_sample_generate(self.h, n, noise and noise.ptr or nil))
+    self.n = n
+end
+function Sampler:score(n, images)             -- images: DeviceTensor NHWC [n][H][W][C] or nil (the sampler's own)
+    self:sync()
+    check(C.fg_sample_score(self.h, n or self.n, images and images.ptr or nil))
+    self.n = n or self.n
+end
+function Sampler:sample(n, noise)
+    self:sync()
+    check(C.fg_sample(self.h, n, noise and noise.ptr or nil))
+    self.n = n
+end
+function Sampler:predictions()                -- host FloatTensor [n] (synchronises)
+    local p = self:ptr(C.FG_SAMPLER_PREDS)
+    local t = torch.FloatTensor(self.n)
+    check(C.fg_d2h(ctx, t:data(), p, self.n * 4))
+    return t
+end
+function Sampler:order(which, k)              -- host table of the k best ('best') / worst ('worst') image indices, 0-based (synchronises)
+    local p = self:ptr(which == 'worst' and C.FG_SAMPLER_ORDER_ASC or C.FG_SAMPLER_ORDER_DESC)
+    k = math.min(k or self.n, self.n)
+    local host = ffi.new('int[?]', k)
+    check(C.fg_d2h(ctx, host, p, k * 4))
+    local t = {}
+    for i = 1, k do t[i] = host[i - 1] end
+    return t
+end
+-- image.toDisplayTensor{input = images, nrow = nrow, padding = padding} over the first k entries of an order: 'best' / 'worst' (the
+-- sampler's rankings), a DeviceTensor holding k int32 indices (0-based), or nil for images 0 .. k-1.  -> host FloatTensor [C][GH][GW],
+-- the one copy back per picture
+function Sampler:grid(order, k, nrow, padding, normalize)
+    padding = padding or 0
+    local optr = nil
+    if order == 'best' then optr = ffi.cast('const int*', (self:ptr(C.FG_SAMPLER_ORDER_DESC)))
+    elseif order == 'worst' then optr = ffi.cast('const int*', (self:ptr(C.FG_SAMPLER_ORDER_ASC)))
+    elseif order then optr = ffi.cast('const int*', order.ptr) end
+    local c, h, w = self.dims[1], self.dims[2], self.dims[3]
+    local xmaps = math.min(nrow, k)
+    local ymaps = math.ceil(k / xmaps)
+    local gh, gw = ymaps * (h + padding), xmaps * (w + padding)
+    local dev = M.DeviceTensor(c * gh * gw)
+    local images = self:ptr(C.FG_SAMPLER_IMAGES)
+    check(C.fg_image_grid(ctx, images, optr, k, c, h, w, nrow, padding, (normalize == false) and 0 or 1, dev.ptr, nil))
+    return dev:float():view(c, gh, gw)
+end
+-- k indices (host, 0-based numbers in a Lua table) -> DeviceTensor of int32 for Sampler:grid
+function M.indexTensor(indices)
+    local k = #indices
+    local host = ffi.new('int[?]', k)
+    for i = 1, k do host[i - 1] = indices[i] end
+    local t = M.DeviceTensor(k)
+    check(C.fg_h2d(ctx, t.ptr, host, k * 4))
+    return t
+end
 
 return M
