@@ -310,11 +310,23 @@ static ConvGeom mk_geom(int b, int h, int w, int cin, int cout, int k, int pad, 
 }
 static inline long long a64(long long v) { return (v + 63) / 64 * 64; }
 
+// What the passes of a thin layer keep in the workspace, in floats, stated once for the size function and for the entries.
+// pass 0 / 1 (forward / data gradient): the packed weights.  pass 2 (weight gradient): FG_THIN_WGRAD_BLOCKS partial slabs of
+// k*k*Cs x Cw floats with their sum behind them; the row-block partials of the bias gradient re-use the front once the slabs are summed.
+static long long thin_ws_floats(int cin, int cout, int k, int pass) {
+    const long long wn = (long long)cin * cout * k * k;
+    if (pass < 2) return wn;
+    const long long slabs = (FG_THIN_WGRAD_BLOCKS + 1) * wn, bias = (long long)CR_ROWBLOCKS_MAX * cout;
+    return slabs > bias ? slabs : bias;
+}
+static int thin_ws_check(fg_ctx* ctx, int cin, int cout, int k, int pass, size_t ws_bytes) {
+    const long long need = thin_ws_floats(cin, cout, k, pass);
+    if ((long long)(ws_bytes / 4) < need) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv2d (thin, pass %d): workspace %zu < %lld bytes", pass, ws_bytes, need * 4);
+    return FG_OK;
+}
+
 size_t fg_conv2d_workspace_bytes(int batch, int h, int w, int cin, int cout, int k, int up) {
-    if (thin_in(cin, cout) || thin_out(cin, cout)) {
-        const long long na = (long long)k * k * (cin <= 4 ? cin : cout), cw = cin <= 4 ? cout : cin;
-        return (size_t)(a64((long long)cin * cout * k * k) + (FG_THIN_WGRAD_BLOCKS + 1) * na * cw + 258LL * (cout > 64 ? cout : 64) + 256) * 4;
-    }
+    if (thin_in(cin, cout) || thin_out(cin, cout)) return (size_t)thin_ws_floats(cin, cout, k, 2) * 4;    // exact: the largest of the passes
     // (no context here: the bound covers both settings of FG_FUSE_WINOGRAD)
     size_t need = 0;
     for (int wn = 0; wn < 2; ++wn) {
@@ -348,6 +360,7 @@ int fg_conv2d_forward(fg_ctx* ctx, const float* x, const float* wt, const float*
     if (rc) return rc;
     if (ws_bytes < fg_conv2d_workspace_bytes(batch, h, w, cin, cout, k, up)) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv2d: workspace");
     float* ws = (float*)wsv;
+    if ((thin_in(cin, cout) || thin_out(cin, cout)) && (rc = thin_ws_check(ctx, cin, cout, k, 0, ws_bytes))) return rc;
     if (thin_in(cin, cout)) {
         if ((rc = fg_launch_thin_pack(ctx, wt, ws, cout, cin, k, 0))) return rc;
         return fg_launch_thin_in_conv(ctx, x, ws, bias, y, batch, h, w, cin, cout, k, 0);
@@ -368,6 +381,7 @@ int fg_conv2d_backward_data(fg_ctx* ctx, const float* gy, const float* wt, float
     if (rc) return rc;
     if (ws_bytes < fg_conv2d_workspace_bytes(batch, h, w, cin, cout, k, up)) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv2d: workspace");
     float* ws = (float*)wsv;
+    if ((thin_in(cin, cout) || thin_out(cin, cout)) && (rc = thin_ws_check(ctx, cin, cout, k, 1, ws_bytes))) return rc;
     if (thin_in(cin, cout)) {  // dX (thin) from dY (wide)
         if ((rc = fg_launch_thin_pack(ctx, wt, ws, cout, cin, k, 0))) return rc;
         return fg_launch_thin_out_conv(ctx, gy, ws, nullptr, gx, batch, h, w, cout, cin, k, 1, 0);
@@ -391,6 +405,7 @@ int fg_conv2d_backward_weight(fg_ctx* ctx, const float* x, const float* gy, floa
     if (thin_in(cin, cout) || thin_out(cin, cout)) {
         const bool tin = thin_in(cin, cout);
         const int cs = tin ? cin : cout, cw = tin ? cout : cin;
+        if ((rc = thin_ws_check(ctx, cin, cout, k, 2, ws_bytes))) return rc;
         float* gwt = ws + (long long)FG_THIN_WGRAD_BLOCKS * k * k * cs * cw;
         rc = tin ? fg_launch_thin_wgrad(ctx, x, gy, gwt, batch, h, w, cs, cw, k, +1, ws)
                  : fg_launch_thin_wgrad(ctx, gy, x, gwt, batch, h, w, cs, cw, k, -1, ws);

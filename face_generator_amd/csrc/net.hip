@@ -860,8 +860,15 @@ int fg_net_out_dims(const fg_net* n, int* c, int* h, int* w) {
 size_t fg_net_workspace_bytes(const fg_net* n, int max_batch) {
     if (!n) return 0;
     fg_net tmp = *n;  // plan on a copy: const query
-    make_plan(&tmp, max_batch);
-    return (size_t)tmp.total_floats * sizeof(float) + 256;
+    // A workspace sized for max_batch is then run at smaller batches (the sampler's tail n % chunk, a last short training batch),
+    // and the need is not monotone in the batch: split-K and the parity split are chosen where the tiles are few, so a smaller batch
+    // can ask for more scratch and more parked weight-gradient partials than a larger one.  The bound covers every batch up to max_batch.
+    long long need = 0;
+    for (int b = 1; b <= max_batch; ++b) {
+        make_plan(&tmp, b);
+        if (tmp.total_floats > need) need = tmp.total_floats;
+    }
+    return (size_t)need * sizeof(float) + 256;
 }
 int fg_net_param_offset(const fg_net* n, int li, long long* wo, long long* wn, long long* bo, long long* bn) {
     if (!n || li < 0 || li >= (int)n->layers.size()) return FG_ERR_INVALID;

@@ -500,6 +500,10 @@ int fg_gan_create(fg_ctx* ctx, fg_net* G, fg_net* D, int table_inputs, int max_b
     }
     if (!rc && !g_fg_dry && hipMemsetAsync(g->ws + g->o_opt[0], 0, (size_t)(2 * g->nP[0]) * 4, ctx->stream) != hipSuccess) rc = fg_set_err(ctx, FG_ERR_HIP, "fg_gan_create: memset");
     if (!rc && !g_fg_dry && hipMemsetAsync(g->ws + g->o_opt[1], 0, (size_t)(2 * g->nP[1]) * 4, ctx->stream) != hipSuccess) rc = fg_set_err(ctx, FG_ERR_HIP, "fg_gan_create: memset");
+    // the result slots read 0 until a closure writes them (FG_GAN_LOSS[1] before the first G-step, the confusion counts before the first D-step):
+    // nothing a caller can read through fg_gan_buffer depends on what the workspace held before
+    if (!rc && !g_fg_dry && (hipMemsetAsync(g->ws + g->o_loss, 0, 4 * 4, ctx->stream) != hipSuccess ||
+                             hipMemsetAsync(g->ws + g->o_conf, 0, 8 * 4, ctx->stream) != hipSuccess)) rc = fg_set_err(ctx, FG_ERR_HIP, "fg_gan_create: memset");
     if (rc) { delete g; return rc; }
     gan_buckets(g, 900000);
     *out = g;

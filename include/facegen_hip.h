@@ -195,6 +195,8 @@ int fg_net_num_masks(const fg_net* net);          /* dropout layers, module orde
 long long fg_net_mask_elems(const fg_net* net, int mask_index, int batch);
 float fg_net_mask_keep(const fg_net* net, int mask_index);   /* Bernoulli keep probability 1 - p of that dropout layer */
 int fg_net_out_dims(const fg_net* net, int* c, int* h, int* w);
+/* covers fg_net_forward / fg_net_backward at EVERY batch from 1 to max_batch (the need is not monotone in the batch: smaller batches
+ * may split their reductions further), so it never shrinks as max_batch grows */
 size_t fg_net_workspace_bytes(const fg_net* net, int max_batch);
 /* offsets (in floats) of layer `layer_index`'s weight / bias inside the flat vector; -1 if it has none */
 int fg_net_param_offset(const fg_net* net, int layer_index, long long* weight_off, long long* weight_n,
@@ -322,8 +324,8 @@ enum fg_gan_buffer_id {
     FG_GAN_D_INPUT = 0,       /* D's batch, NHWC [B][H][W][C]: real || fake (D-step), G's samples (G-step)            */
     FG_GAN_NOISE = 1,         /* the noise the last closure used when the library drew it                              */
     FG_GAN_D_GRAD_INPUT = 2,  /* G-step: d loss / d samples                                                           */
-    FG_GAN_LOSS = 3,          /* float[2]: BCE of the last D-step, of the last G-step                                  */
-    FG_GAN_CONFUSION = 4,     /* int[8] (same storage as floats): local counts, global counts                         */
+    FG_GAN_LOSS = 3,          /* float[2]: BCE of the last D-step, of the last G-step (0 until that step has run)      */
+    FG_GAN_CONFUSION = 4,     /* int[8] (same storage as floats): local counts, global counts (0 until a D-step ran)  */
     FG_GAN_OPT_STATE_D = 5,   /* 2 * nparams(D): Adam m | v   (SGD: momentum buffer; Adagrad: variance)                */
     FG_GAN_OPT_STATE_G = 6,
     FG_GAN_D_OUTPUT = 7,      /* D's probabilities [B] of the last closure; offset relative to D's OWN workspace       */
@@ -431,6 +433,10 @@ int fg_c2f_coarse_diff(fg_ctx* ctx, const float* fine, float* coarse, float* dif
 
 /* ---- module-level ops (nn.Module protocol: updateOutput / updateGradInput / accGradParameters), NHWC ----
  * conv / linear take REFERENCE-layout weights and pack them into `ws` on the fly. */
+/* fg_conv2d_workspace_bytes / fg_linear_workspace_bytes: what ANY of the three passes needs at this shape, whatever fg_set_math,
+ * fg_set_fusion and fg_test_set_wino_wgrad_thresholds say when the pass runs (the functions take no context: the bound covers every
+ * setting).  ws: 256-byte aligned; the passes read nothing of it that they did not write in the same call and write nothing
+ * outside [ws, ws + ws_bytes). */
 size_t fg_conv2d_workspace_bytes(int batch, int h, int w, int cin, int cout, int k, int upsample2x);
 int fg_conv2d_forward(fg_ctx* ctx, const float* x, const float* w_oihw, const float* bias, float* y, int batch, int h,
                       int w, int cin, int cout, int k, int pad, int upsample2x, void* ws, size_t ws_bytes);
@@ -470,6 +476,7 @@ int fg_actpool_backward(fg_ctx* ctx, const float* x, const float* gy, const floa
                         float* scratch);
 int fg_spatial_dropout_apply(fg_ctx* ctx, const float* x, const float* mask, float mscale, float* y, int batch, int hw,
                              int c);
+/* h and w even (FG_ERR_INVALID otherwise, nothing is launched) */
 int fg_avgpool2x2_forward(fg_ctx* ctx, const float* x, float* y, int batch, int h, int w, int c);
 int fg_avgpool2x2_backward(fg_ctx* ctx, const float* gy, float* gx, int batch, int h, int w, int c);
 int fg_upsample_nearest2x_forward(fg_ctx* ctx, const float* x, float* y, int batch, int h, int w, int c);
@@ -479,7 +486,8 @@ int fg_upsample_nearest2x_backward(fg_ctx* ctx, const float* gy, float* gx, int 
  * forward: conv output -> viewed output; backward: gradient wrt the viewed output -> gradient wrt the conv output. */
 int fg_conv_upsample_view_forward(fg_ctx* ctx, const float* conv_out, float* viewed, int batch, int h, int w, int c, int factor);
 int fg_conv_upsample_view_backward(fg_ctx* ctx, const float* g_viewed, float* g_conv_out, int batch, int h, int w, int c, int factor);
-/* nn.SpatialMaxPooling(2,2): backward recomputes the argmax (first max in scan order) from the saved input */
+/* nn.SpatialMaxPooling(2,2): backward recomputes the argmax (first max in scan order) from the saved input.  h and w even, and
+ * for the forward pass c % 4 == 0 (FG_ERR_INVALID otherwise, nothing is launched) */
 int fg_maxpool2x2_forward(fg_ctx* ctx, const float* x, float* y, int batch, int h, int w, int c);
 int fg_maxpool2x2_backward(fg_ctx* ctx, const float* x, const float* gy, float* gx, int batch, int h, int w, int c);
 /* nn.Dropout on any shape: y = x * mask * scale (mask NULL: y = x * scale) */

@@ -2,6 +2,16 @@ import numpy as np
 import torch
 
 
+# The bars of the module-level parity tests (tests/test_gpu_ops.py), named so that tests/test_gpu_memory_contract.py holds the same
+# entries to the same bars without restating them.  conv_* / lin / bn_gx / bn_gparam scale with max(1, max|reference|); *_rtol are relative.
+BAR = dict(conv_fwd=2e-5, conv_dgrad=2e-5, conv_wgrad=3e-5, conv_bgrad=3e-5, conv_acc=1e-5, lin=2e-5,
+           bn_y=2e-5, bn_mean=1e-6, bn_invstd_rtol=2e-6, bn_running_mean=1e-6, bn_running_var_rtol=1e-5, bn_gx=3e-5, bn_gparam=2e-5,
+           prelu=1e-6, slope_grad=1e-4, upsample_fwd=0.0, upsample_bwd=1e-6, avgpool_fwd=1e-6, avgpool_bwd=1e-7, sigmoid=1e-6,
+           leakyrelu=1e-6,
+           wino_fwd=3e-5, wino_dgrad=3e-5, wino_wgrad=4e-5,       # tests/test_gpu_wino.py: the Winograd kernels against the oracle
+           bce_loss_rtol=1e-5, bce_grad_atol=1e-7, bce_grad_rtol=1e-5, norms_rtol=1e-5)
+
+
 def nhwc(a, dev):
     """numpy NCHW -> device NHWC tensor (test plumbing only)."""
     t = torch.tensor(np.ascontiguousarray(a), dtype=torch.float32, device=dev)

@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from oracle import torch7_nn as O
-from gpu_util import nhwc, nchw, dev, close
+from gpu_util import nhwc, nchw, dev, close, BAR
 
 pytestmark = pytest.mark.gpu
 
@@ -67,16 +67,16 @@ def test_conv2d_forward_backward(ctx, B, H, W, Cin, Cout, k, up):
     w_d, b_d = dev(conv.weight, d), dev(conv.bias, d)
     y_d = ops.conv2d_forward(nhwc(x, d), w_d, b_d, upsample2x=bool(up))
     scale = np.abs(y).max()
-    close(nchw(y_d), y, atol=2e-5 * max(scale, 1), what="conv fwd")
+    close(nchw(y_d), y, atol=BAR["conv_fwd"] * max(scale, 1), what="conv fwd")
     gx_d = ops.conv2d_backward_data(nhwc(gy, d), w_d, (H, W), upsample2x=bool(up))
-    close(nchw(gx_d), gx, atol=2e-5 * max(np.abs(gx).max(), 1), what="conv dgrad")
+    close(nchw(gx_d), gx, atol=BAR["conv_dgrad"] * max(np.abs(gx).max(), 1), what="conv dgrad")
     gw_d, gb_d = ops.conv2d_backward_weight(nhwc(x, d), nhwc(gy, d), k, upsample2x=bool(up))
-    close(gw_d.cpu().numpy(), conv.gradWeight, atol=3e-5 * max(np.abs(conv.gradWeight).max(), 1), what="conv wgrad")
-    close(gb_d.cpu().numpy(), conv.gradBias, atol=3e-5 * max(np.abs(conv.gradBias).max(), 1), what="conv bgrad")
+    close(gw_d.cpu().numpy(), conv.gradWeight, atol=BAR["conv_wgrad"] * max(np.abs(conv.gradWeight).max(), 1), what="conv wgrad")
+    close(gb_d.cpu().numpy(), conv.gradBias, atol=BAR["conv_bgrad"] * max(np.abs(conv.gradBias).max(), 1), what="conv bgrad")
     # accumulate semantics (Torch accGradParameters): beta = 1 doubles
     gw2, gb2 = ops.conv2d_backward_weight(nhwc(x, d), nhwc(gy, d), k, upsample2x=bool(up), gw=gw_d.clone(),
                                           gb=gb_d.clone(), beta=1.0)
-    close(gw2.cpu().numpy(), 2 * gw_d.cpu().numpy(), atol=1e-5 * max(np.abs(conv.gradWeight).max(), 1), what="acc")
+    close(gw2.cpu().numpy(), 2 * gw_d.cpu().numpy(), atol=BAR["conv_acc"] * max(np.abs(conv.gradWeight).max(), 1), what="acc")
 
 
 @pytest.mark.parametrize("B,K,N", [(4, 100, 8192), (6, 2048, 512), (128, 512, 512), (3, 64, 128), (130, 100, 256),
@@ -91,11 +91,11 @@ def test_linear(ctx, B, K, N):
     gx = lin.backward(x, gy)
     d = ctx.device
     w_d, b_d = dev(lin.weight, d), dev(lin.bias, d)
-    close(ops.linear_forward(dev(x, d), w_d, b_d).cpu().numpy(), y, atol=2e-5 * max(np.abs(y).max(), 1), what="lin fwd")
-    close(ops.linear_backward_data(dev(gy, d), w_d).cpu().numpy(), gx, atol=2e-5 * max(np.abs(gx).max(), 1), what="lin dgrad")
+    close(ops.linear_forward(dev(x, d), w_d, b_d).cpu().numpy(), y, atol=BAR["lin"] * max(np.abs(y).max(), 1), what="lin fwd")
+    close(ops.linear_backward_data(dev(gy, d), w_d).cpu().numpy(), gx, atol=BAR["lin"] * max(np.abs(gx).max(), 1), what="lin dgrad")
     gw, gb = ops.linear_backward_weight(dev(x, d), dev(gy, d))
-    close(gw.cpu().numpy(), lin.gradWeight, atol=2e-5 * max(np.abs(lin.gradWeight).max(), 1), what="lin wgrad")
-    close(gb.cpu().numpy(), lin.gradBias, atol=2e-5 * max(np.abs(lin.gradBias).max(), 1), what="lin bgrad")
+    close(gw.cpu().numpy(), lin.gradWeight, atol=BAR["lin"] * max(np.abs(lin.gradWeight).max(), 1), what="lin wgrad")
+    close(gb.cpu().numpy(), lin.gradBias, atol=BAR["lin"] * max(np.abs(lin.gradBias).max(), 1), what="lin bgrad")
 
 
 @pytest.mark.parametrize("B,H,W,C,prelu", [(4, 16, 16, 256, True), (3, 7, 5, 128, True), (2, 8, 8, 64, False),
@@ -116,23 +116,23 @@ def test_batchnorm_prelu(ctx, B, H, W, C, prelu):
     rm, rv = ctx.zeros(C), torch.ones(C, device=d)
     slope = dev(pr.weight, d) if prelu else None
     y_d, mean, invstd = ops.batchnorm_forward(nhwc(x, d), dev(bn.weight, d), dev(bn.bias, d), slope, rm, rv)
-    close(nchw(y_d), y, atol=2e-5, what="bn fwd")
-    close(mean.cpu().numpy(), bn.save_mean, atol=1e-6, what="bn mean")
-    close(invstd.cpu().numpy(), bn.save_invstd, atol=0, rtol=2e-6, what="bn invstd")
-    close(rm.cpu().numpy(), bn.running_mean, atol=1e-6, what="running_mean")
-    close(rv.cpu().numpy(), bn.running_var, atol=0, rtol=1e-5, what="running_var")
+    close(nchw(y_d), y, atol=BAR["bn_y"], what="bn fwd")
+    close(mean.cpu().numpy(), bn.save_mean, atol=BAR["bn_mean"], what="bn mean")
+    close(invstd.cpu().numpy(), bn.save_invstd, atol=0, rtol=BAR["bn_invstd_rtol"], what="bn invstd")
+    close(rm.cpu().numpy(), bn.running_mean, atol=BAR["bn_running_mean"], what="running_mean")
+    close(rv.cpu().numpy(), bn.running_var, atol=0, rtol=BAR["bn_running_var_rtol"], what="running_var")
     gx_d, gg, gb, gs = ops.batchnorm_backward(nhwc(x, d), nhwc(gy, d), dev(bn.weight, d), dev(bn.bias, d), mean, invstd, slope)
-    close(nchw(gx_d), gx, atol=3e-5 * max(1, np.abs(gx).max()), what="bn gx")
-    close(gg.cpu().numpy(), bn.gradWeight, atol=2e-5 * max(1, np.abs(bn.gradWeight).max()), what="bn ggamma")
-    close(gb.cpu().numpy(), bn.gradBias, atol=2e-5 * max(1, np.abs(bn.gradBias).max()), what="bn gbeta")
+    close(nchw(gx_d), gx, atol=BAR["bn_gx"] * max(1, np.abs(gx).max()), what="bn gx")
+    close(gg.cpu().numpy(), bn.gradWeight, atol=BAR["bn_gparam"] * max(1, np.abs(bn.gradWeight).max()), what="bn ggamma")
+    close(gb.cpu().numpy(), bn.gradBias, atol=BAR["bn_gparam"] * max(1, np.abs(bn.gradBias).max()), what="bn gbeta")
     if prelu:
-        close(gs.cpu().numpy(), pr.gradWeight, atol=2e-5 * max(1, abs(pr.gradWeight[0])), what="slope grad")
+        close(gs.cpu().numpy(), pr.gradWeight, atol=BAR["bn_gparam"] * max(1, abs(pr.gradWeight[0])), what="slope grad")
     # evaluate mode uses the running statistics (sample.lua path)
     bn.evaluate()
     ze = bn.forward(x)
     ye = pr.forward(ze) if prelu else ze
     ye_d, _, _ = ops.batchnorm_forward(nhwc(x, d), dev(bn.weight, d), dev(bn.bias, d), slope, rm, rv, train=False)
-    close(nchw(ye_d), ye, atol=2e-5, what="bn eval")
+    close(nchw(ye_d), ye, atol=BAR["bn_y"], what="bn eval")
 
 
 def test_prelu_dropout_and_actpool(ctx):
@@ -149,10 +149,10 @@ def test_prelu_dropout_and_actpool(ctx):
     gy = rng.standard_normal(y.shape).astype(np.float32)
     gx = pr.backward(x, dr.backward(pr.output, gy))
     sl = dev(pr.weight, d)
-    close(ops.prelu_forward(dev(x, d), sl, dev(mask, d), 2.0).cpu().numpy(), y, atol=1e-6, what="prelu+drop fwd")
+    close(ops.prelu_forward(dev(x, d), sl, dev(mask, d), 2.0).cpu().numpy(), y, atol=BAR["prelu"], what="prelu+drop fwd")
     gx_d, gs = ops.prelu_backward(dev(x, d), dev(gy, d), sl, dev(mask, d), 2.0)
-    close(gx_d.cpu().numpy(), gx, atol=1e-6, what="prelu+drop gx")
-    close(gs.cpu().numpy(), pr.gradWeight, atol=1e-4, what="prelu slope grad")
+    close(gx_d.cpu().numpy(), gx, atol=BAR["prelu"], what="prelu+drop gx")
+    close(gs.cpu().numpy(), pr.gradWeight, atol=BAR["slope_grad"], what="prelu slope grad")
     # PReLU + SpatialDropout(0.2) + AvgPool  (models.lua:386-388)
     B, C, H, W = 3, 64, 8, 8
     x = rng.standard_normal((B, C, H, W)).astype(np.float32)
@@ -164,10 +164,10 @@ def test_prelu_dropout_and_actpool(ctx):
     gy = rng.standard_normal(y.shape).astype(np.float32)
     gx = pr.backward(x, sd.backward(pr.output, ap.backward(sd.output, gy)))
     sl = dev(pr.weight, d)
-    close(nchw(ops.actpool_forward(nhwc(x, d), sl, dev(m, d))), y, atol=1e-6, what="actpool fwd")
+    close(nchw(ops.actpool_forward(nhwc(x, d), sl, dev(m, d))), y, atol=BAR["prelu"], what="actpool fwd")
     gx_d, gs = ops.actpool_backward(nhwc(x, d), nhwc(gy, d), sl, dev(m, d))
-    close(nchw(gx_d), gx, atol=1e-6, what="actpool gx")
-    close(gs.cpu().numpy(), pr.gradWeight, atol=1e-4, what="actpool slope grad")
+    close(nchw(gx_d), gx, atol=BAR["prelu"], what="actpool gx")
+    close(gs.cpu().numpy(), pr.gradWeight, atol=BAR["slope_grad"], what="actpool slope grad")
     # evaluate mode: y = (1-p) * x, no mask
     sd.evaluate()
     ye = ap.forward(sd.forward(pr.forward(x)))
@@ -183,31 +183,31 @@ def test_small_pointwise(ctx):
     y = ctx.empty(B, 2 * H, 2 * W, C)
     ctx.check(lib.fg_upsample_nearest2x_forward(ctx.h, xd.data_ptr(), y.data_ptr(), B, H, W, C))
     up = O.SpatialUpSamplingNearest(2)
-    close(nchw(y), up.forward(x), atol=0, what="upsample fwd")
+    close(nchw(y), up.forward(x), atol=BAR["upsample_fwd"], what="upsample fwd")
     gy = rng.standard_normal((B, C, 2 * H, 2 * W)).astype(np.float32)
     gx = ctx.empty(B, H, W, C)
     ctx.check(lib.fg_upsample_nearest2x_backward(ctx.h, nhwc(gy, d).data_ptr(), gx.data_ptr(), B, H, W, C))
-    close(nchw(gx), up.backward(x, gy), atol=1e-6, what="upsample bwd")
+    close(nchw(gx), up.backward(x, gy), atol=BAR["upsample_bwd"], what="upsample bwd")
     ap = O.SpatialAveragePooling()
     yp = ctx.empty(B, H // 2, W // 2, C)
     ctx.check(lib.fg_avgpool2x2_forward(ctx.h, xd.data_ptr(), yp.data_ptr(), B, H, W, C))
-    close(nchw(yp), ap.forward(x[:, :, :H // 2 * 2, :]), atol=1e-6, what="avgpool fwd")
+    close(nchw(yp), ap.forward(x[:, :, :H // 2 * 2, :]), atol=BAR["avgpool_fwd"], what="avgpool fwd")
     g2 = rng.standard_normal((B, C, H // 2, W // 2)).astype(np.float32)
     gxp = ctx.empty(B, H, W, C)
     ctx.check(lib.fg_avgpool2x2_backward(ctx.h, nhwc(g2, d).data_ptr(), gxp.data_ptr(), B, H, W, C))
-    close(nchw(gxp), ap.backward(x, g2), atol=1e-7, what="avgpool bwd")
+    close(nchw(gxp), ap.backward(x, g2), atol=BAR["avgpool_bwd"], what="avgpool bwd")
     sg = O.Sigmoid()
     ys = torch.empty_like(xd)
     ctx.check(lib.fg_sigmoid_forward(ctx.h, xd.data_ptr(), ys.data_ptr(), xd.numel()))
-    close(nchw(ys), sg.forward(x), atol=1e-6, what="sigmoid")
+    close(nchw(ys), sg.forward(x), atol=BAR["sigmoid"], what="sigmoid")
     lr = O.LeakyReLU(0.333)
     yl = torch.empty_like(xd)
     ctx.check(lib.fg_leakyrelu_forward(ctx.h, xd.data_ptr(), 0.333, yl.data_ptr(), xd.numel()))
-    close(nchw(yl), lr.forward(x), atol=1e-6, what="leakyrelu")
+    close(nchw(yl), lr.forward(x), atol=BAR["leakyrelu"], what="leakyrelu")
     gl = torch.empty_like(xd)
     gyl = rng.standard_normal(x.shape).astype(np.float32)
     ctx.check(lib.fg_leakyrelu_backward(ctx.h, xd.data_ptr(), nhwc(gyl, d).data_ptr(), 0.333, gl.data_ptr(), xd.numel()))
-    close(nchw(gl), lr.backward(x, gyl), atol=1e-6, what="leakyrelu bwd")
+    close(nchw(gl), lr.backward(x, gyl), atol=BAR["leakyrelu"], what="leakyrelu bwd")
     # layout round trip
     back = ctx.to_nchw(ctx.to_device_nhwc(torch.tensor(x)))
     close(back.cpu().numpy(), x, atol=0, what="nchw<->nhwc")
@@ -225,8 +225,8 @@ def test_bce_and_confusion(ctx):
         f = crit.forward(p.reshape(B, 1), t)
         g = crit.backward(p.reshape(B, 1), t)
         loss, grad, conf = BCECriterion().forward_backward_device(ctx, dev(p, ctx.device), dev(t, ctx.device))
-        assert abs(loss.item() - f) <= 1e-5 * abs(f)          # loss: rel 1e-5
-        close(grad.cpu().numpy(), g[:, 0], atol=1e-7, rtol=1e-5, what="bce grad")
+        assert abs(loss.item() - f) <= BAR["bce_loss_rtol"] * abs(f)          # loss: rel 1e-5
+        close(grad.cpu().numpy(), g[:, 0], atol=BAR["bce_grad_atol"], rtol=BAR["bce_grad_rtol"], what="bce grad")
         want = np.zeros(4, np.int64)
         for i in range(B):
             want[(2 if p[i] > 0.5 else 0) + int(t[i])] += 1
@@ -281,8 +281,8 @@ def test_fused_adam_sgd_adagrad_match_reference_formulas(ctx):
     out = ctx.empty(2); scr = ctx.empty(1024)
     ctx.check(ctx.lib.fg_norms(ctx.h, dev(p0, d).data_ptr(), n, out.data_ptr(), scr.data_ptr()))
     o = out.cpu().numpy()
-    assert abs(o[0] - np.abs(p0.astype(np.float64)).sum()) < 1e-5 * o[0]
-    assert abs(o[1] - (p0.astype(np.float64) ** 2).sum()) < 1e-5 * o[1]
+    assert abs(o[0] - np.abs(p0.astype(np.float64)).sum()) < BAR["norms_rtol"] * o[0]
+    assert abs(o[1] - (p0.astype(np.float64) ** 2).sum()) < BAR["norms_rtol"] * o[1]
 
 
 def test_philox_rng(ctx):

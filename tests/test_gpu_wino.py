@@ -15,7 +15,7 @@ import pytest
 import torch
 
 from oracle import torch7_nn as O
-from gpu_util import nhwc, nchw, dev, close
+from gpu_util import nhwc, nchw, dev, close, BAR
 
 pytestmark = pytest.mark.gpu
 
@@ -63,8 +63,8 @@ def test_winograd_forward_and_data_gradient(ctx, B, H, W, Cin, Cout):
     yw, gw = got[FG_FUSE_DEFAULT]
     yi, gi = got[FG_FUSE_DEFAULT & ~FG_FUSE_WINOGRAD]
     sy, sg = max(np.abs(y).max(), 1.0), max(np.abs(gx).max(), 1.0)
-    close(yw, y, atol=3e-5 * sy, what="winograd forward vs oracle")
-    close(gw, gx, atol=3e-5 * sg, what="winograd data gradient vs oracle")
+    close(yw, y, atol=BAR["wino_fwd"] * sy, what="winograd forward vs oracle")
+    close(gw, gx, atol=BAR["wino_dgrad"] * sg, what="winograd data gradient vs oracle")
     close(yi, y, atol=2e-5 * sy, what="implicit GEMM forward vs oracle")
     close(yw, yi, atol=3e-5 * sy, what="winograd vs implicit GEMM forward")
     close(gw, gi, atol=3e-5 * sg, what="winograd vs implicit GEMM data gradient")
@@ -130,8 +130,8 @@ def test_winograd_up_and_5x5_layers(ctx, B, H, W, Cin, Cout, k, up):
     yw, gw = got[FG_FUSE_DEFAULT]
     yi, gi = got[FG_FUSE_DEFAULT & ~WINO_ALL]
     sy, sg = max(np.abs(y).max(), 1.0), max(np.abs(gx).max(), 1.0)
-    close(yw, y, atol=3e-5 * sy, what="winograd forward vs oracle")
-    close(gw, gx, atol=3e-5 * sg, what="winograd data gradient vs oracle")
+    close(yw, y, atol=BAR["wino_fwd"] * sy, what="winograd forward vs oracle")
+    close(gw, gx, atol=BAR["wino_dgrad"] * sg, what="winograd data gradient vs oracle")
     close(yw, yi, atol=3e-5 * sy, what="winograd vs implicit GEMM forward")
     close(gw, gi, atol=3e-5 * sg, what="winograd vs implicit GEMM data gradient")
     assert not np.array_equal(yw, yi), "both settings of the Winograd bits gave identical bits: the switch selected nothing"
@@ -232,7 +232,7 @@ def test_winograd_weight_gradient(ctx, B, H, W, Cin, Cout, k, up):
     # G^T . G mixes them with weights 1, 1/2, 1/4: a few fp32 roundings of the largest position sum -- 4e-5 * max|gradW| (the
     # tap-by-tap contraction meets 3e-5)
     sw, sb = max(np.abs(conv.gradWeight).max(), 1.0), max(np.abs(conv.gradBias).max(), 1.0)
-    close(gw, conv.gradWeight, atol=4e-5 * sw, what="winograd weight gradient vs oracle")
+    close(gw, conv.gradWeight, atol=BAR["wino_wgrad"] * sw, what="winograd weight gradient vs oracle")
     close(gw0, conv.gradWeight, atol=3e-5 * sw, what="tap-by-tap weight gradient vs oracle")
     close(gb, conv.gradBias, atol=3e-5 * sb, what="bias gradient (winograd kernel's partial sums) vs oracle")
     close(gb0, conv.gradBias, atol=3e-5 * sb, what="bias gradient vs oracle")
