@@ -300,8 +300,9 @@ int fg_norms(fg_ctx* ctx, const float* p, long long n, float* out2, float* scrat
 }
 
 // ---------------------------------------------------------------- module-level conv / linear
-static bool thin_in(int cin, int cout) { return cin <= 4 && cout % 64 == 0; }
-static bool thin_out(int cin, int cout) { return cout <= 4 && cin % 64 == 0; }
+// (fg_thin_layer, fg_internal.h: true only where the forward, the data gradient and the weight gradient all have a thin instance)
+static bool thin_in(int cin, int cout, int k) { return fg_thin_layer(cin, cout, k); }
+static bool thin_out(int cin, int cout, int k) { return fg_thin_layer(cout, cin, k); }
 static ConvGeom mk_geom(int b, int h, int w, int cin, int cout, int k, int pad, int up, int fusion = 0) {
     ConvGeom g; memset(&g, 0, sizeof(g));
     g.B = b; g.H = h; g.W = w; g.Cin = cin; g.Cout = cout; g.k = k; g.pad = pad; g.fold = up;
@@ -326,7 +327,7 @@ static int thin_ws_check(fg_ctx* ctx, int cin, int cout, int k, int pass, size_t
 }
 
 size_t fg_conv2d_workspace_bytes(int batch, int h, int w, int cin, int cout, int k, int up) {
-    if (thin_in(cin, cout) || thin_out(cin, cout)) return (size_t)thin_ws_floats(cin, cout, k, 2) * 4;    // exact: the largest of the passes
+    if (thin_in(cin, cout, k) || thin_out(cin, cout, k)) return (size_t)thin_ws_floats(cin, cout, k, 2) * 4;    // exact: the largest of the passes
     // (no context here: the bound covers both settings of FG_FUSE_WINOGRAD)
     size_t need = 0;
     for (int wn = 0; wn < 2; ++wn) {
@@ -340,11 +341,12 @@ size_t fg_conv2d_workspace_bytes(int batch, int h, int w, int cin, int cout, int
 }
 static int conv_check(fg_ctx* ctx, int cin, int cout, int k, int pad, int up) {
     if (k % 2 != 1 || pad != (k - 1) / 2) return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "conv2d: only odd-k 'same' stride-1");
-    if (thin_in(cin, cout) || thin_out(cin, cout)) {
+    if (thin_in(cin, cout, k) || thin_out(cin, cout, k)) {
         if (up) return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "conv2d: upsample fold on a thin conv");
         return FG_OK;
     }
-    // (any channel count: a ragged one -- nInputPlane / nOutputPlane % 4 != 0 -- takes a zero-padded copy of the operand, conv_ops.hip)
+    // (any other channel count, the 1- to 4-channel layers without a full set of thin instances included: a ragged one -- nInputPlane /
+    // nOutputPlane % 4 != 0 -- takes a zero-padded copy of the operand, conv_ops.hip)
     if (up) {
         int T, rmin;
         fg_fold_window(k, pad, &T, &rmin);
@@ -360,12 +362,12 @@ int fg_conv2d_forward(fg_ctx* ctx, const float* x, const float* wt, const float*
     if (rc) return rc;
     if (ws_bytes < fg_conv2d_workspace_bytes(batch, h, w, cin, cout, k, up)) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv2d: workspace");
     float* ws = (float*)wsv;
-    if ((thin_in(cin, cout) || thin_out(cin, cout)) && (rc = thin_ws_check(ctx, cin, cout, k, 0, ws_bytes))) return rc;
-    if (thin_in(cin, cout)) {
+    if ((thin_in(cin, cout, k) || thin_out(cin, cout, k)) && (rc = thin_ws_check(ctx, cin, cout, k, 0, ws_bytes))) return rc;
+    if (thin_in(cin, cout, k)) {
         if ((rc = fg_launch_thin_pack(ctx, wt, ws, cout, cin, k, 0))) return rc;
         return fg_launch_thin_in_conv(ctx, x, ws, bias, y, batch, h, w, cin, cout, k, 0);
     }
-    if (thin_out(cin, cout)) {
+    if (thin_out(cin, cout, k)) {
         if ((rc = fg_launch_thin_pack(ctx, wt, ws, cout, cin, k, 1))) return rc;
         return fg_launch_thin_out_conv(ctx, x, ws, bias, y, batch, h, w, cin, cout, k, 0, 0);
     }
@@ -381,12 +383,12 @@ int fg_conv2d_backward_data(fg_ctx* ctx, const float* gy, const float* wt, float
     if (rc) return rc;
     if (ws_bytes < fg_conv2d_workspace_bytes(batch, h, w, cin, cout, k, up)) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv2d: workspace");
     float* ws = (float*)wsv;
-    if ((thin_in(cin, cout) || thin_out(cin, cout)) && (rc = thin_ws_check(ctx, cin, cout, k, 1, ws_bytes))) return rc;
-    if (thin_in(cin, cout)) {  // dX (thin) from dY (wide)
+    if ((thin_in(cin, cout, k) || thin_out(cin, cout, k)) && (rc = thin_ws_check(ctx, cin, cout, k, 1, ws_bytes))) return rc;
+    if (thin_in(cin, cout, k)) {  // dX (thin) from dY (wide)
         if ((rc = fg_launch_thin_pack(ctx, wt, ws, cout, cin, k, 0))) return rc;
         return fg_launch_thin_out_conv(ctx, gy, ws, nullptr, gx, batch, h, w, cout, cin, k, 1, 0);
     }
-    if (thin_out(cin, cout)) {
+    if (thin_out(cin, cout, k)) {
         if ((rc = fg_launch_thin_pack(ctx, wt, ws, cout, cin, k, 1))) return rc;
         return fg_launch_thin_in_conv(ctx, gy, ws, nullptr, gx, batch, h, w, cout, cin, k, 1);
     }
@@ -402,8 +404,8 @@ int fg_conv2d_backward_weight(fg_ctx* ctx, const float* x, const float* gy, floa
     if (rc) return rc;
     if (ws_bytes < fg_conv2d_workspace_bytes(batch, h, w, cin, cout, k, up)) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv2d: workspace");
     float* ws = (float*)wsv;
-    if (thin_in(cin, cout) || thin_out(cin, cout)) {
-        const bool tin = thin_in(cin, cout);
+    if (thin_in(cin, cout, k) || thin_out(cin, cout, k)) {
+        const bool tin = thin_in(cin, cout, k);
         const int cs = tin ? cin : cout, cw = tin ? cout : cin;
         if ((rc = thin_ws_check(ctx, cin, cout, k, 2, ws_bytes))) return rc;
         float* gwt = ws + (long long)FG_THIN_WGRAD_BLOCKS * k * k * cs * cw;

@@ -685,8 +685,8 @@ int fg_net_create(fg_ctx* ctx, const fg_layer_spec* L, int nl, int in_c, int in_
                     if ((h & 1) || (w & 1) || l.c * l.c > FG_MAX_GROUPS) { fail(FG_ERR_UNSUPPORTED, "stride-2 conv: even H/W", i); break; }
                     s.oh = h / 2; s.ow = w / 2; s.kind = ST_CONV;
                 } else
-                if (l.a <= 4 && l.b % 64 == 0) s.kind = ST_THIN_IN;
-                else if (l.b <= 4 && l.a % 64 == 0) {
+                if (fg_thin_layer(l.a, l.b, l.c)) s.kind = ST_THIN_IN;
+                else if (fg_thin_layer(l.b, l.a, l.c)) {
                     s.kind = ST_THIN_OUT;
                     if (i + 1 < nl && L[i + 1].type == FG_SIGMOID && !(l.q > 1.f)) { s.has_sigmoid = 1; consumed = 2; }
                 } else if (l.c * l.c <= FG_MAX_GROUPS) { s.kind = ST_CONV; fg_geom_set_wino(g, ctx->fusion); }   // 3x3: Winograd F(2x2, 3x3)

@@ -1623,6 +1623,7 @@ __global__ __launch_bounds__(256) void gemv_bwd_kernel(const float* __restrict__
 // expressions of prelu_bwd_kernel -- and every sum (weight gradient rows, bias gradient, slope gradient) leaves per-block partials
 // for the deferred final of the pass (fixed order).  One launch instead of two, 64 blocks instead of 8.
 #define GEMV_BWD_ROWS 16
+#define GEMV_BWD_CHUNK 8192
 __global__ __launch_bounds__(256) void gemv_bwd_act_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ y, const float* __restrict__ gy,
                                                            float* __restrict__ gx, float* __restrict__ gwp, float* __restrict__ gbp,
@@ -1696,9 +1697,15 @@ int fg_launch_gemv_backward(fg_ctx* ctx, const float* x, const float* w, const f
             return FG_OK;
         }
     }
-    hipLaunchKernelGGL(gemv_bwd_kernel, dim3(fg_cdiv(K, 64)), dim3(256), (B + 256) * sizeof(float), ctx->stream, x, w, y,
-                       gy, gx, gw, gb, acc, B, K, sigmoid);
-    FG_CHECK_LAUNCH(ctx);
+    // the kernel keeps its rows' dl[] in LDS: at most GEMV_BWD_CHUNK rows per launch (33 KB), later chunks accumulate onto the first
+    // (one launch asked for (B + 256) * 4 bytes: above 64 KB -- B > 16128 -- the launch was refused, above 160 KB it cannot exist)
+    for (int b0 = 0; b0 < B; b0 += GEMV_BWD_CHUNK) {
+        const int nb = B - b0 < GEMV_BWD_CHUNK ? B - b0 : GEMV_BWD_CHUNK;
+        hipLaunchKernelGGL(gemv_bwd_kernel, dim3(fg_cdiv(K, 64)), dim3(256), (nb + 256) * sizeof(float), ctx->stream,
+                           x ? x + (size_t)b0 * K : x, w, y ? y + b0 : y, gy + b0, gx ? gx + (size_t)b0 * K : gx, gw, gb,
+                           b0 ? 1.f : acc, nb, K, sigmoid);
+        FG_CHECK_LAUNCH(ctx);
+    }
     return FG_OK;
 }
 

@@ -436,7 +436,16 @@ int fg_c2f_coarse_diff(fg_ctx* ctx, const float* fine, float* coarse, float* dif
 /* fg_conv2d_workspace_bytes / fg_linear_workspace_bytes: what ANY of the three passes needs at this shape, whatever fg_set_math,
  * fg_set_fusion and fg_test_set_wino_wgrad_thresholds say when the pass runs (the functions take no context: the bound covers every
  * setting).  ws: 256-byte aligned; the passes read nothing of it that they did not write in the same call and write nothing
- * outside [ws, ws + ws_bytes). */
+ * outside [ws, ws + ws_bytes).
+ * Geometries: fg_conv2d_* take odd k <= 7 with pad = (k - 1) / 2 ('same', stride 1) at ANY channel counts, and the three passes
+ * accept exactly the same ones: a geometry either runs forward, data gradient and weight gradient or gets the same error code from
+ * all three.  Refused (FG_ERR_UNSUPPORTED) are only, with upsample2x = 1 (the folded nearest-x2 upsample):
+ *   - k = 7 (the folded window needs more tap groups than the kernels hold), and
+ *   - a THIN layer: 1 or 3 channels on one side (also 4 at k = 3) against 64, 128 or a multiple of 256 on the other.  Those layers
+ *     have kernels of their own (the image-side convolutions of the models), without a folded form.
+ * Every other layer with few channels on one side (2 channels; 4 at 5x5 / 7x7; widths such as 192 or 320) is an ordinary
+ * convolution on zero-padded channel rows.  fg_net_create classifies a FG_CONV layer the same way.
+ * Linear(in_f -> 1) runs as a matrix-vector product at any batch. */
 size_t fg_conv2d_workspace_bytes(int batch, int h, int w, int cin, int cout, int k, int upsample2x);
 int fg_conv2d_forward(fg_ctx* ctx, const float* x, const float* w_oihw, const float* bias, float* y, int batch, int h,
                       int w, int cin, int cout, int k, int pad, int upsample2x, void* ws, size_t ws_bytes);

@@ -1,0 +1,178 @@
+"""CPU-only: every kernel plan that a caller of the conv / linear C entries can reach is compared with a reference by some
+operator-level GPU parity case; the three conv passes accept the same geometries; every launch site in csrc/*.hip is entered in
+tests/DISPATCH_COVERAGE.md.  All of it from planning-only child processes with FG_LAUNCH_LOG=1 (tests/dispatch_audit.py), like
+tests/test_branched_host.py and tests/test_sampler_host.py."""
+import os
+import re
+import time
+
+import pytest
+
+import dispatch_audit as A
+
+LDS_MAX = 160 * 1024            # CDNA4: LDS of one workgroup
+LDS_PLAIN = 64 * 1024           # dynamic LDS a launch may ask for without hipFuncAttributeMaxDynamicSharedMemorySize
+# Kernels whose dynamic LDS is an arithmetic function of the geometry (rows x width of the map, the batch), not one of a few tile
+# configurations: their signature is (launch site, block) alone -- DISPATCH_COVERAGE.md, "Known limits".
+SHAPE_SIZED_LDS = {"thin_out_slab_mfma_kernel", "gemv_bwd_kernel"}
+STATUSES = {"operator", "net-only", "measure-only", "unreachable", "other-entry"}
+
+
+def norm(sig):
+    return (sig[0], sig[1], None) if A.kernel_of(sig[0]) in SHAPE_SIZED_LDS else sig
+
+
+def matches(expect, sig):
+    return expect[0] == sig[0] and expect[1] == sig[1] and (expect[2] is None or expect[2] == sig[2])
+
+
+@pytest.fixture(scope="module")
+def audit():
+    from face_generator_amd import build
+    build.build(verbose=False)
+    t0 = time.time()
+    out = dict(replay=A.replay(), sweep=A.sweep(), nets=A.net_launches())
+    out["seconds"] = time.time() - t0
+    return out
+
+
+def thin_layer(cs, cw, k):
+    """csrc/fg_internal.h fg_thin_layer, restated from include/facegen_hip.h"""
+    return (cw in (64, 128) or cw % 256 == 0) and ((k == 3 and cs in (1, 3, 4)) or (k in (5, 7) and cs in (1, 3)))
+
+
+def test_the_sweep_is_the_one_the_ledger_describes(audit):
+    conv, lin = A.sweep_geometries()
+    assert len(conv) >= 1500 and len(lin) >= 300
+    assert {c[5] for c in conv} == {3, 5, 7} and {c[6] for c in conv} == {0, 1}
+    assert {c[3] for c in conv} == set(A.CHANNELS) == {c[4] for c in conv}
+    assert max(c[0] for c in conv) == 128 and min(c[0] for c in conv) == 1
+    pow2 = sum(1 for c in conv if c[1] & (c[1] - 1) == 0 and c[2] & (c[2] - 1) == 0)
+    assert 0.4 * len(conv) < pow2 < 0.65 * len(conv)
+    assert all(max(c[3], c[4]) * c[0] * c[1] * c[2] * (4 if c[6] else 1) <= A.CAP for c in conv)
+    assert any(b >= 65536 and k <= 16 for b, k, n in lin) and any(b <= 4 and k >= 16384 for b, k, n in lin)
+    assert {(j["math"], j["fusion"]) for j in audit["sweep"] if j["kind"] == "conv"} == \
+        {(0, 503), (6, 503), (0, 503 & ~A.WINO_ALL), (6, 503 & ~A.WINO_ALL), (0, 503 & ~A.THIN_SLAB)}
+    text = open(A.LEDGER).read()
+    assert "seed %d" % A.SWEEP_SEED in text and "%d conv geometries" % len(conv) in text and "%d Linear shapes" % len(lin) in text
+    print("replay + sweep + net logs: %.1f s" % audit["seconds"])
+    assert audit["seconds"] < 120
+
+
+def test_every_reachable_signature_is_covered_by_an_operator_level_case(audit):
+    """(a) no exception list: whatever signature the sweep reaches through fg_conv2d_* / fg_linear_*, some parity list runs it"""
+    covered = {norm(s) for s in A.all_sigs(audit["replay"])}
+    best = A.smallest_per_signature(audit["sweep"])
+    missing = sorted((s for s in A.all_sigs(audit["sweep"]) if norm(s) not in covered), key=str)
+    assert not missing, "reachable but never compared with a reference:\n" + "\n".join("%s  smallest: %s" % (s, best.get(s)) for s in missing)
+
+
+def test_the_new_cases_take_the_signatures_written_next_to_them(audit):
+    import test_gpu_dispatch_paths as TP
+    jobs = {j["case"]: j for j in audit["replay"] if j["list"] == "PATH_CASES"}
+    assert sorted(jobs) == sorted(c.name for c in TP.PATH_CASES) and len(jobs) == len(TP.PATH_CASES)
+    for c in TP.PATH_CASES:
+        j = jobs[c.name]
+        assert all(j["rc"][p][0] == 0 for p in A.PASSES), (c.name, j["rc"])
+        for p, want in c.expect.items():
+            for e in want:
+                assert any(matches(e, s) for s in j["sigs"][p]), "%s %s: expected %s, launched %s" % (c.name, p, e, j["sigs"][p])
+    # the ledger names every case: removing one from the GPU module shows here even where another case shares its signature
+    listed = re.findall(r"^\| `([\w.-]+)` \| (?:conv|lin) ", open(A.LEDGER).read(), flags=re.M)
+    assert sorted(listed) == sorted(jobs), set(listed) ^ set(jobs)
+
+
+def test_the_three_conv_passes_accept_the_same_geometries(audit):
+    """(b) forward, data gradient and weight gradient all run or all return the same code; fg_conv2d_workspace_bytes is enough for
+    the ones that run (the entries got exactly that many bytes); odd k <= 7 with 'same' padding is refused only for the two
+    reasons include/facegen_hip.h states: the folded upsample on a thin layer, and the folded upsample at 7x7."""
+    bad = []
+    for j in audit["sweep"]:
+        codes = {p: j["rc"][p][0] for p in A.PASSES}
+        if j["kind"] == "lin":
+            if any(codes.values()):
+                bad.append((j["shape"], j["rc"]))
+            continue
+        B, H, W, cin, cout, k, up = j["shape"]
+        stated = bool(up) and (k == 7 or thin_layer(cin, cout, k) or thin_layer(cout, cin, k))
+        want = -4 if stated else 0          # FG_ERR_UNSUPPORTED
+        if any(c != want for c in codes.values()):
+            bad.append((j["shape"], j["math"], j["fusion"], {p: j["rc"][p] for p in A.PASSES}))
+    assert not bad, "%d geometries; first: %s" % (len(bad), bad[:5])
+
+
+def test_nets_with_reclassified_layers_plan_and_run_forward_and_backward():
+    """fg_net_create asks the same predicate as the module-level entries: the gray coarse-to-fine generator (first layer 2 -> 64 at
+    3x3) and a chain 4 -> 64 (5x5) -> 192 -> 1 are created, run forward and run backward with parameter gradients (before
+    fg_thin_layer the first one planned, ran forward and was refused in its backward: "thin_wgrad: k=3 Cs=2 not built"), their
+    few-channel layers as implicit GEMMs with a weight-gradient launch each, the 256 -> 1 7x7 head still on the thin kernels."""
+    nets = A.reclassified_net_launches()
+    names = {t: [A.sig_of(l)[0] for l in v] for t, v in nets.items()}
+    g = names["gray-c2f-G"]
+    assert g.count("(igemm_kernel<BM, BN, BK>)") == 1 and g.count("(wgrad_kernel<BT, BK, OCC>)") == 4, g     # 2 -> 64 + three wide layers
+    assert not any("thin_in_generic" in n for n in g) and any(n.startswith("(thin_wgrad_mfma_kernel<7, 1") for n in g), g
+    c = names["few-channel-chain"]
+    assert c.count("(wgrad_kernel<BT, BK, OCC>)") == 3 and not any("thin" in n for n in c), c
+
+
+def test_no_launch_asks_for_more_lds_than_the_launcher_arranged(audit):
+    """a launch above 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize set on that kernel, and nothing above
+    160 KB exists -- a planning-only run returns FG_OK for such a launch, a device refuses it.  (The check is by kernel NAME: a
+    template one of whose instances raises the limit passes for all its instances.)"""
+    src = "".join(open(os.path.join(A.CSRC, f)).read() for f in sorted(os.listdir(A.CSRC)) if f.endswith(".hip"))
+    raised = set(re.findall(r"hipFuncSetAttribute\(\(const void\*\)\s*([A-Za-z_]\w*)", src))
+    bad = {}
+    for j in audit["sweep"] + audit["replay"]:
+        for v in j["sigs"].values():
+            for s in v:
+                if s[2] > LDS_MAX or (s[2] > LDS_PLAIN and A.kernel_of(s[0]) not in raised):
+                    bad.setdefault(s, j["shape"])
+    assert not bad, bad
+
+
+def measure_only_sites():
+    """kernel names all of whose launch sites sit inside #ifdef FG_MEASURE"""
+    inside, outside = set(), set()
+    for fn in sorted(os.listdir(A.CSRC)):
+        if not fn.endswith(".hip"):
+            continue
+        stack = []
+        for line in open(os.path.join(A.CSRC, fn)):
+            t = line.strip()
+            if re.match(r"#\s*if", t):
+                stack.append("M" if re.match(r"#\s*ifdef\s+FG_MEASURE\b", t) else "-")
+            elif re.match(r"#\s*else", t) and stack:
+                stack[-1] = {"M": "-", "-": "-"}[stack[-1]]
+            elif re.match(r"#\s*endif", t) and stack:
+                stack.pop()
+            for m in re.finditer(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*)", line):
+                (inside if "M" in stack else outside).add(m.group(1))
+    return inside - outside
+
+
+def test_every_launch_site_is_entered_in_the_ledger_with_one_status(audit):
+    """(c) the census"""
+    sites = A.launch_sites()
+    rows = A.ledger_rows()
+    assert sorted(rows) == sorted(sites), "ledger and csrc/*.hip disagree: %s" % sorted(set(rows) ^ set(sites))
+    assert all(st in STATUSES for st, _ in rows.values()), {k: v for k, v in rows.items() if v[0] not in STATUSES}
+    repk = {A.kernel_of(s[0]) for s in A.all_sigs(audit["replay"])}
+    swk = {A.kernel_of(s[0]) for s in A.all_sigs(audit["sweep"])}
+    netk = {A.kernel_of(A.sig_of(l)[0]) for v in audit["nets"].values() for l in v}
+    meas = measure_only_sites()
+    tests = set(os.listdir(os.path.join(A.ROOT, "tests")))
+    for k, (st, note) in sorted(rows.items()):
+        if st == "operator":
+            assert k in repk, "%s: not seen in the replay" % k
+        elif st == "net-only":
+            assert k in netk and k not in repk, "%s: net-only means seen in the net logs and not in the replay" % k
+            assert any(t in tests for t in re.findall(r"test_gpu_\w+\.py", note)), "%s: name the GPU test that runs it" % k
+        elif st == "measure-only":
+            assert k in meas, "%s: has a launch site outside #ifdef FG_MEASURE" % k
+        elif st == "unreachable":
+            assert k not in repk | swk | netk and k not in meas, "%s is reached" % k
+            assert len(note) > 20, "%s: say which earlier branch shadows it" % k
+        else:       # other-entry: launched by entries outside the conv / linear contraction family
+            assert k not in repk | swk | netk and k not in meas, k
+            assert any(t in tests for t in re.findall(r"test_gpu_\w+\.py", note)), "%s: name the GPU test of its entry" % k
+    assert meas <= {k for k, v in rows.items() if v[0] == "measure-only"}

@@ -40,6 +40,22 @@ def test_fusion_flags_roundtrip_and_reject_unknown_bits(ctx):
 def test_prelu_in_epilogue_equals_separate_passes(ctx, S, B):
     """c2f G_d and D_c forward + backward with the PReLUs folded into the contraction epilogues vs as passes of their own.
     (64, 8) selects the wave-specialised kernels of the BASELINE size, (16, 4) the 64x64-tile kernels."""
+    prelu_fused_equals_separate(ctx, S, B, FG_FUSE_ALL)
+
+
+def test_prelu_in_epilogue_of_the_implicit_gemm_kernels(ctx):
+    """The same with the Winograd bits cleared while the nets are created (the bits are read then): at 64 px the 3x3 / 5x5 layers run
+    as implicit GEMMs, and the PReLU rides on igemm_ws_act_kernel, igemm_ws64x3_kernel<1> / <2> and igemm_act_kernel<.., 2> --
+    launch sites that no net with the default bits reaches (tests/DISPATCH_COVERAGE.md)."""
+    base = FG_FUSE_ALL & ~(32 | 64 | 128 | 256)
+    ctx.set_fusion(base)
+    try:
+        prelu_fused_equals_separate(ctx, 64, 8, base)
+    finally:
+        ctx.set_fusion(FG_FUSE_DEFAULT)
+
+
+def prelu_fused_equals_separate(ctx, S, B, base):
     st, Gd, Dd, rng = build(ctx, S, B, seed=900 + S)
     d = ctx.device
     cond = rng.uniform(0, 1, (B, 3, S, S)).astype(np.float32)
@@ -49,7 +65,7 @@ def test_prelu_in_epilogue_equals_separate_passes(ctx, S, B):
     gyo = rng.standard_normal((B, 1)).astype(np.float32)
     masks = dev_masks(masks_for(rng, B, S), d)
     res = {}
-    for flags in (FG_FUSE_ALL, FG_FUSE_ALL & ~FG_FUSE_PRELU):
+    for flags in (base, base & ~FG_FUSE_PRELU):
         ctx.set_fusion(flags)
         dn = Gd.inner.device_net
         y = dn.forward(Gd.combine_device(ctx, nhwc(noise, d), nhwc(cond, d))).clone()
@@ -61,7 +77,7 @@ def test_prelu_in_epilogue_equals_separate_passes(ctx, S, B):
         gD = dnD.grads.clone()
         res[flags] = (y, gG, yd, gx, gD)
     ctx.set_fusion(FG_FUSE_DEFAULT)
-    a, b = res[FG_FUSE_ALL], res[FG_FUSE_ALL & ~FG_FUSE_PRELU]
+    a, b = res[base], res[base & ~FG_FUSE_PRELU]
     assert torch.equal(a[0], b[0]), "G output"
     assert torch.equal(a[2], b[2]), "D output"
     assert torch.equal(a[3], b[3]), "D gradInput"
@@ -80,8 +96,10 @@ def test_prelu_in_epilogue_equals_separate_passes(ctx, S, B):
         assert off == ga.numel()
 
 
-@pytest.mark.parametrize("B,H,W,Cw,Cs,flip", [(3, 32, 32, 128, 3, 0), (128, 32, 32, 128, 3, 0), (5, 16, 16, 64, 1, 0),
-                                               (2, 64, 64, 64, 3, 1), (4, 8, 8, 128, 3, 1)])
+SLAB_CASES = [(3, 32, 32, 128, 3, 0), (128, 32, 32, 128, 3, 0), (5, 16, 16, 64, 1, 0), (2, 64, 64, 64, 3, 1), (4, 8, 8, 128, 3, 1)]
+
+
+@pytest.mark.parametrize("B,H,W,Cw,Cs,flip", SLAB_CASES)
 def test_thin_output_3x3_slab_kernel_equals_window_kernel_and_oracle(ctx, B, H, W, Cw, Cs, flip):
     """flip = 0: forward of a Cw -> Cs convolution; flip = 1: the data gradient of a Cs -> Cw convolution (the same kernel
     with mirrored taps), through the module-level entries."""

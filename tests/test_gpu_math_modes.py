@@ -29,8 +29,10 @@ def rel_rms(a, ref):
 
 # (B, H, W, Cin, Cout, k, folded nearest-x2): G's two big layers (models.lua:64-69), D's 128->256 (models.lua:395), and a
 # small batch that reaches the bf16x6 kernels through split-K
-@pytest.mark.parametrize("shape", [(128, 16, 16, 256, 128, 5, 1), (128, 8, 8, 128, 256, 5, 1), (128, 8, 8, 128, 256, 3, 0),
-                                   (16, 16, 16, 256, 128, 5, 1)])
+BF16X6_SHAPES = [(128, 16, 16, 256, 128, 5, 1), (128, 8, 8, 128, 256, 5, 1), (128, 8, 8, 128, 256, 3, 0), (16, 16, 16, 256, 128, 5, 1)]
+
+
+@pytest.mark.parametrize("shape", BF16X6_SHAPES)
 def test_bf16x6_contractions_are_not_less_accurate_than_fp32_mfma(ctx, shape):
     from face_generator_amd import ops
     B, H, W, Cin, Cout, k, up = shape

@@ -79,8 +79,11 @@ def test_conv2d_forward_backward(ctx, B, H, W, Cin, Cout, k, up):
     close(gw2.cpu().numpy(), 2 * gw_d.cpu().numpy(), atol=BAR["conv_acc"] * max(np.abs(conv.gradWeight).max(), 1), what="acc")
 
 
-@pytest.mark.parametrize("B,K,N", [(4, 100, 8192), (6, 2048, 512), (128, 512, 512), (3, 64, 128), (130, 100, 256),
-                                   (5, 50, 256), (4, 99, 8192), (7, 64, 10), (6, 33, 7)])      # --noiseDim 50 / 99 (nn_utils.lua:35-39); ragged both ways
+LINEAR_CASES = [(4, 100, 8192), (6, 2048, 512), (128, 512, 512), (3, 64, 128), (130, 100, 256),
+                (5, 50, 256), (4, 99, 8192), (7, 64, 10), (6, 33, 7)]      # --noiseDim 50 / 99 (nn_utils.lua:35-39); ragged both ways
+
+
+@pytest.mark.parametrize("B,K,N", LINEAR_CASES)
 def test_linear(ctx, B, K, N):
     from face_generator_amd import ops
     rng = np.random.default_rng(B + K + N)
