@@ -339,10 +339,13 @@ size_t fg_conv2d_workspace_bytes(int batch, int h, int w, int cin, int cout, int
     }
     return need;
 }
-static int conv_check(fg_ctx* ctx, int cin, int cout, int k, int pad, int up) {
+// one answer for forward, data gradient and weight gradient of a geometry, before any of them launches anything
+static int conv_check(fg_ctx* ctx, int batch, int h, int w, int cin, int cout, int k, int pad, int up) {
     if (k % 2 != 1 || pad != (k - 1) / 2) return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "conv2d: only odd-k 'same' stride-1");
     if (thin_in(cin, cout, k) || thin_out(cin, cout, k)) {
         if (up) return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "conv2d: upsample fold on a thin conv");
+        if (!fg_thin_fits(batch, h, w, cin > cout ? cin : cout))
+            return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "conv2d: thin conv with an operand of 2^31 floats or more (%d x %d x %d x %d)", batch, h, w, cin > cout ? cin : cout);
         return FG_OK;
     }
     // (any other channel count, the 1- to 4-channel layers without a full set of thin instances included: a ragged one -- nInputPlane /
@@ -358,7 +361,7 @@ static int conv_check(fg_ctx* ctx, int cin, int cout, int k, int pad, int up) {
 int fg_conv2d_forward(fg_ctx* ctx, const float* x, const float* wt, const float* bias, float* y, int batch, int h,
                       int w, int cin, int cout, int k, int pad, int up, void* wsv, size_t ws_bytes) {
     NEED(ctx, ctx && x && wt && y && wsv, "null argument");
-    int rc = conv_check(ctx, cin, cout, k, pad, up);
+    int rc = conv_check(ctx, batch, h, w, cin, cout, k, pad, up);
     if (rc) return rc;
     if (ws_bytes < fg_conv2d_workspace_bytes(batch, h, w, cin, cout, k, up)) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv2d: workspace");
     float* ws = (float*)wsv;
@@ -379,7 +382,7 @@ int fg_conv2d_forward(fg_ctx* ctx, const float* x, const float* wt, const float*
 int fg_conv2d_backward_data(fg_ctx* ctx, const float* gy, const float* wt, float* gx, int batch, int h, int w, int cin,
                             int cout, int k, int pad, int up, void* wsv, size_t ws_bytes) {
     NEED(ctx, ctx && gy && wt && gx && wsv, "null argument");
-    int rc = conv_check(ctx, cin, cout, k, pad, up);
+    int rc = conv_check(ctx, batch, h, w, cin, cout, k, pad, up);
     if (rc) return rc;
     if (ws_bytes < fg_conv2d_workspace_bytes(batch, h, w, cin, cout, k, up)) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv2d: workspace");
     float* ws = (float*)wsv;
@@ -400,7 +403,7 @@ int fg_conv2d_backward_data(fg_ctx* ctx, const float* gy, const float* wt, float
 int fg_conv2d_backward_weight(fg_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, float beta, int batch,
                               int h, int w, int cin, int cout, int k, int pad, int up, void* wsv, size_t ws_bytes) {
     NEED(ctx, ctx && x && gy && gw && wsv, "null argument");
-    int rc = conv_check(ctx, cin, cout, k, pad, up);
+    int rc = conv_check(ctx, batch, h, w, cin, cout, k, pad, up);
     if (rc) return rc;
     if (ws_bytes < fg_conv2d_workspace_bytes(batch, h, w, cin, cout, k, up)) return fg_set_err(ctx, FG_ERR_WORKSPACE, "conv2d: workspace");
     float* ws = (float*)wsv;

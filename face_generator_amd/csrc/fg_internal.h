@@ -437,14 +437,18 @@ int fg_launch_zero_insert2(fg_ctx*, const float* g, float* out, int B, int H, in
 // thin convolutions (3 <-> wide channels), NHWC, stride 1, "same" pad, odd k <= 7
 // Which layers take them: Cs = 1 or 3 thin channels at k = 3, 5, 7 (Cs = 4 at k = 3 only) against Cw = 64, 128 or a multiple of 256
 // wide ones -- exactly the geometries at which fg_launch_thin_in_conv, fg_launch_thin_out_conv AND fg_launch_thin_wgrad each hold an
-// instance (operands below 2^31 floats), so a layer that runs forward also runs both gradients.  Every other layer with few channels
+// instance, so a layer that runs forward also runs both gradients.  Every other layer with few channels
 // on one side (Cs = 2; Cs = 4 at 5x5 / 7x7; Cw = 192, 320, ...) is an ordinary convolution: the implicit GEMM pads ragged channel
 // counts (conv_ops.hip pad_operand).  The module-level entries (api.hip) and fg_net_create (net.hip) both ask this one function.
+// The size rule beside it, fg_thin_fits: the wide operand B*H*W*Cw of a thin layer stays below 2^31 floats (the kernels index it
+// with 32 bits).  A thin layer that does not fit is REFUSED, in all three passes alike (conv_check in api.hip, fg_net_forward in
+// net.hip), not sent elsewhere; the three launchers take both predicates as preconditions and hold no fallback kernel.
 static inline bool fg_thin_layer(int cs, int cw, int k) {
     if (!(cw == 64 || cw == 128 || (cw > 0 && cw % 256 == 0))) return false;
     if (k == 3) return cs == 1 || cs == 3 || cs == 4;
     return (k == 5 || k == 7) && (cs == 1 || cs == 3);
 }
+static inline bool fg_thin_fits(int B, int H, int W, int cw) { return (long long)B * H * W * cw < (1LL << 31); }
 // thin-in : out[pix][c<Cw] = bias[c] + sum_{tap, s<Cs} in[pix+off(tap)][s] * Wp[tap][s][c]
 // actf / actb (optional, MFMA variants only; ->applied says whether it happened): the PReLU behind (forward) / in front of
 // (data gradient of a thin-output layer) the layer, folded into the epilogue like IgemmArgs::act_*

@@ -1037,6 +1037,9 @@ int fg_net_forward_to(fg_net* n, int B, const float* x, void* wsv, size_t ws_byt
     fg_ctx* ctx = n->ctx;
     if (!n->params) return fg_set_err(ctx, FG_ERR_INVALID, "fg_net_forward: fg_net_bind first");
     if (B <= 0) return fg_set_err(ctx, FG_ERR_INVALID, "fg_net_forward: batch %d", B);
+    for (const Stage& s : n->st)        // the size rule of the thin layers (fg_thin_fits): refused here, before anything is launched
+        if ((s.kind == ST_THIN_IN || s.kind == ST_THIN_OUT) && !fg_thin_fits(B, s.ih, s.iw, s.kind == ST_THIN_IN ? s.oc : s.ic))
+            return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "fg_net_forward: layer %d: thin conv with an operand of 2^31 floats or more at batch %d", s.first_layer, B);
     if (((uintptr_t)wsv & 15) || ((uintptr_t)x & 15)) return fg_set_err(ctx, FG_ERR_INVALID, "fg_net_forward: 16-byte alignment");
     if (train && n->n_masks > 0 && (!masks || n_masks != n->n_masks))
         return fg_set_err(ctx, FG_ERR_INVALID, "fg_net_forward: %d dropout masks required in training mode", n->n_masks);

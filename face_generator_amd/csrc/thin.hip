@@ -1,7 +1,13 @@
 // "Thin" convolutions for gfx950: one side of the contraction has <= 4 channels (image side of the nets:
 // D's first conv 3->64 and G's last conv 128->3, models.lua:385 / :73, and their data / weight gradients).
-// N or K of the GEMM view is 3 (or 27), so MFMA tiles would be > 90 % padding: these are HBM/VALU-bound and
-// run on the vector ALU with coalesced NHWC accesses and weights held in registers.
+// Which layers come here is fg_thin_layer / fg_thin_fits (fg_internal.h); each launcher refuses anything else.  What runs them:
+//   matrix pipe (v_mfma_f32_32x32x2_f32, the thin axis padded to one 32-wide tile):
+//     thin-in   thin_in_mfma_kernel (3x3, Cs = 1 | 3), thin_in_mfma_lds_kernel (3x3 Cs = 4; 5x5 / 7x7),
+//               thin_in_mfma_pad_kernel (5x5 / 7x7 from a zero-bordered copy, power-of-two maps)
+//     thin-out  thin_out_slab_mfma_kernel (3x3), thin_out_rows_mfma_kernel + thin_out_rows_gather_kernel (5x5 / 7x7 forward)
+//     wgrad     thin_wgrad_mfma_kernel (every layer)
+//   vector ALU (thin-out only, coalesced NHWC loads, weights in registers or LDS tiles): thin_out_win_kernel / thin_out_kernel
+//     (3x3 where the slab does not apply), thin_out_tiled_kernel (wide or 5x5 / 7x7 layers), thin_out_generic_kernel (Cs = 4)
 #include "fg_internal.h"
 // FG_THIN_DBG (drop the gathers / the stores of thin_in_mfma_kernel: timing experiments, WRONG results) exists only in builds with
 // -DFG_MEASURE; the production kernel carries no such branch
@@ -23,239 +29,7 @@ __device__ __forceinline__ float wave_sum_x(float v) {
 
 // ---------------------------------------------------------------------------------
 // thin-in: out[pix][c] = bias[c] + sum_{tap,s} in[pix + off(tap)][s] * Wp[tap][s][c]     (Cs small, Cw wide)
-// block = 256 threads = CBLK channels x PL pixel lanes; weights for channel c live in registers.
 // ---------------------------------------------------------------------------------
-// One wave per pixel (wave-uniform pixel index): the CS-channel input taps are the same for all 64 lanes, so they
-// are fetched through the scalar cache (s_load) and feed v_fmac as SGPR operands; each lane owns CJ output channels
-// whose weights stay in registers.  Stores are 256 B coalesced per wave.
-template <int K, int CS, int CJ>
-__global__ __launch_bounds__(256) void thin_in_kernel(const float* __restrict__ in, const float* __restrict__ Wp,
-                                                      const float* __restrict__ bias, float* __restrict__ out, int B,
-                                                      int H, int W, int flip, int Cw) {
-    constexpr int PAD = (K - 1) / 2;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int cb = blockIdx.y * (CJ * 64) + lane;       // this lane's first output channel
-    float w[K * K * CS][CJ];
-#pragma unroll
-    for (int t = 0; t < K * K * CS; ++t)
-#pragma unroll
-        for (int j = 0; j < CJ; ++j) w[t][j] = Wp[(size_t)t * Cw + cb + 64 * j];
-    float bv[CJ];
-#pragma unroll
-    for (int j = 0; j < CJ; ++j) bv[j] = bias ? bias[cb + 64 * j] : 0.f;
-    const int npix = B * H * W;
-    const int nwaves = gridDim.x * 4;
-    // two pixels per iteration; every tap is loaded from a clamped (always valid) wave-uniform address and zeroed by a
-    // scalar select, so all 2*K*K scalar loads of an iteration are issued before the first use (one latency, not K)
-    for (int pix0 = blockIdx.x * 4 + wave; pix0 < npix; pix0 += 2 * nwaves) {
-        float v[2][K * K * CS];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int pix = min(pix0 + u * nwaves, npix - 1);
-            const int x = pix % W;
-            const int t = pix / W;
-            const int y = t % H;
-            const int b = t / H;
-#pragma unroll
-            for (int dy = 0; dy < K; ++dy) {
-                const int yy = y + (flip ? PAD - dy : dy - PAD);
-                const int yc = min(max(yy, 0), H - 1);
-#pragma unroll
-                for (int dx = 0; dx < K; ++dx) {
-                    const int xx = x + (flip ? PAD - dx : dx - PAD);
-                    const int xc = min(max(xx, 0), W - 1);
-                    const bool ok = yy == yc && xx == xc;
-                    const float* ip = in + ((size_t)(b * H + yc) * W + xc) * CS;   // wave-uniform address
-#pragma unroll
-                    for (int s = 0; s < CS; ++s) {
-                        const float tv = ip[s];
-                        v[u][(dy * K + dx) * CS + s] = ok ? tv : 0.f;
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int pix = pix0 + u * nwaves;
-            if (pix >= npix) break;
-            float acc[CJ];
-#pragma unroll
-            for (int j = 0; j < CJ; ++j) acc[j] = bv[j];
-#pragma unroll
-            for (int t = 0; t < K * K * CS; ++t)
-#pragma unroll
-                for (int j = 0; j < CJ; ++j) acc[j] = fmaf(v[u][t], w[t][j], acc[j]);
-#pragma unroll
-            for (int j = 0; j < CJ; ++j) out[(size_t)pix * Cw + cb + 64 * j] = acc[j];
-        }
-    }
-}
-
-// 3x3 thin-in, one wave per image ROW: the wave walks x with a sliding 3x3xCS window held in scalar registers (one new
-// column = 3 scalar loads per pixel, no per-pixel index arithmetic); the x loop is unrolled by 3 so the window slots
-// rotate statically.  Weights are pre-flipped for the data-grad form, so the loop body is always a correlation.
-template <int CS, int CJ>
-__global__ __launch_bounds__(256) void thin_in_row3_kernel(const float* __restrict__ in, const float* __restrict__ Wp,
-                                                           const float* __restrict__ bias, float* __restrict__ out,
-                                                           int B, int H, int W, int flip, int Cw) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int cb = blockIdx.y * (CJ * 64) + lane;
-    float w[9 * CS][CJ];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int s = 0; s < CS; ++s)
-#pragma unroll
-            for (int j = 0; j < CJ; ++j) w[t * CS + s][j] = Wp[(size_t)((flip ? 8 - t : t) * CS + s) * Cw + cb + 64 * j];
-    float bv[CJ];
-#pragma unroll
-    for (int j = 0; j < CJ; ++j) bv[j] = bias ? bias[cb + 64 * j] : 0.f;
-    const int row = blockIdx.x * 4 + wave;            // (b, y), wave-uniform
-    if (row >= B * H) return;
-    const int y = row % H;
-    const float* rp[3];
-    bool rok[3];
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-        const int yy = y + dy - 1;
-        rok[dy] = (unsigned)yy < (unsigned)H;
-        rp[dy] = in + (size_t)(row + (rok[dy] ? dy - 1 : 0)) * W * CS;
-    }
-    float win[3][3][CS];                               // [column slot][row][channel]
-#define FG_LOADCOL(slot, xc)                                                                        \
-    {                                                                                               \
-        const bool cok = (unsigned)(xc) < (unsigned)W;                                              \
-        const int xcl = cok ? (xc) : 0;                                                             \
-        _Pragma("unroll") for (int dy = 0; dy < 3; ++dy)                                            \
-            _Pragma("unroll") for (int s = 0; s < CS; ++s) {                                        \
-                const float tv = rp[dy][xcl * CS + s];                                              \
-                win[slot][dy][s] = (cok && rok[dy]) ? tv : 0.f;                                     \
-            }                                                                                       \
-    }
-    FG_LOADCOL(2, -1)                                  // column -1 lives in slot (-1 mod 3) = 2
-    FG_LOADCOL(0, 0)
-    float* orow = out + (size_t)row * W * Cw + cb;
-    for (int x0 = 0; x0 < W; x0 += 3) {
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {
-            const int x = x0 + u;
-            if (x >= W) break;
-            FG_LOADCOL((u + 1) % 3, x + 1)
-            float acc[CJ];
-#pragma unroll
-            for (int j = 0; j < CJ; ++j) acc[j] = bv[j];
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-                    for (int s = 0; s < CS; ++s)
-#pragma unroll
-                        for (int j = 0; j < CJ; ++j)
-                            acc[j] = fmaf(win[(u + dx + 2) % 3][dy][s], w[(dy * 3 + dx) * CS + s][j], acc[j]);
-#pragma unroll
-            for (int j = 0; j < CJ; ++j) orow[(size_t)x * Cw + 64 * j] = acc[j];
-        }
-    }
-#undef FG_LOADCOL
-}
-
-// Large-kernel thin-in (c2f generator head data-grad: 7x7, 3 -> 256): a strip of TR image rows (+ halo, zero padded) of
-// the thin operand is staged in LDS; each wave computes NPX consecutive output pixels per step for its 64 channels,
-// reading every halo row segment once (uniform-address LDS broadcast) and re-using it for the NPX pixels; the K*K*CS
-// weights of the lane's channel stay in registers (pre-flipped for the data-grad form).
-template <int K, int CS>
-__global__ __launch_bounds__(256) void thin_in_rows_kernel(const float* __restrict__ in, const float* __restrict__ Wp,
-                                                           const float* __restrict__ bias, float* __restrict__ out,
-                                                           int B, int H, int W, int flip, int Cw) {
-    constexpr int PAD = (K - 1) / 2;
-    constexpr int TR = 4, NPX = 4;
-    constexpr int SEG = (NPX + K - 1) * CS;            // floats of one halo row segment
-    constexpr int SEG4 = (SEG + 3) / 4 * 4;
-    extern __shared__ __attribute__((aligned(16))) float tile[];
-    const int WP = (W + 2 * PAD + 3) / 4 * 4 + 4;      // padded row length in pixels (room for the last float4)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = blockIdx.y * 64 + lane;
-    float w[K * K * CS];
-#pragma unroll
-    for (int t = 0; t < K * K; ++t)
-#pragma unroll
-        for (int s = 0; s < CS; ++s) w[t * CS + s] = Wp[(size_t)((flip ? K * K - 1 - t : t) * CS + s) * Cw + c];
-    const float bv = bias ? bias[c] : 0.f;
-    const int strips_per_img = (H + TR - 1) / TR;
-    const int b = blockIdx.x / strips_per_img, y0 = (blockIdx.x - b * strips_per_img) * TR;
-    for (int i = threadIdx.x; i < (TR + 2 * PAD) * WP * CS; i += 256) {
-        const int s = i % CS;
-        const int t = i / CS;
-        const int xx = t % WP - PAD, yy = y0 + t / WP - PAD;
-        float v = 0.f;
-        if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) v = in[((size_t)(b * H + yy) * W + xx) * CS + s];
-        tile[i] = v;
-    }
-    __syncthreads();
-    const int rows = min(TR, H - y0);
-    const int gpr = (W + NPX - 1) / NPX;               // pixel groups per row
-    for (int grp = wave; grp < rows * gpr; grp += 4) {
-        const int r = grp / gpr, x0 = (grp - r * gpr) * NPX;
-        float acc[NPX];
-#pragma unroll
-        for (int q = 0; q < NPX; ++q) acc[q] = bv;
-#pragma unroll
-        for (int dy = 0; dy < K; ++dy) {
-            float seg[SEG4];
-            const float* sp = tile + ((r + dy) * WP + x0) * CS;     // wave-uniform address
-#pragma unroll
-            for (int i = 0; i < SEG4; ++i) seg[i] = sp[i];
-#pragma unroll
-            for (int dx = 0; dx < K; ++dx)
-#pragma unroll
-                for (int s = 0; s < CS; ++s)
-#pragma unroll
-                    for (int q = 0; q < NPX; ++q) acc[q] = fmaf(seg[(q + dx) * CS + s], w[(dy * K + dx) * CS + s], acc[q]);
-            __builtin_amdgcn_sched_barrier(0);   // keep one row segment live at a time (else 7 x 32 VGPRs get hoisted)
-        }
-#pragma unroll
-        for (int q = 0; q < NPX; ++q)
-            if (x0 + q < W) out[((size_t)(b * H + y0 + r) * W + x0 + q) * Cw + c] = acc[q];
-    }
-}
-
-// generic fallback: runtime k / Cs, weights re-read through L1
-__global__ __launch_bounds__(256) void thin_in_generic_kernel(const float* __restrict__ in, const float* __restrict__ Wp,
-                                                              const float* __restrict__ bias, float* __restrict__ out,
-                                                              int B, int H, int W, int Cs, int Cw, int K, int flip,
-                                                              int cblk) {
-    const int PAD = (K - 1) / 2;
-    const int pl = threadIdx.x / cblk, tc = threadIdx.x - pl * cblk;
-    const int PL = 256 / cblk;
-    const int c = blockIdx.y * cblk + tc;
-    const float bv = bias ? bias[c] : 0.f;
-    const int npix = B * H * W;
-    const int p0 = blockIdx.x * 128;
-    for (int j = pl; j < 128; j += PL) {
-        const int pix = p0 + j;
-        if (pix >= npix) break;
-        const int x = pix % W;
-        const int t = pix / W;
-        const int y = t % H;
-        const int b = t / H;
-        float acc = bv;
-        for (int dy = 0; dy < K; ++dy) {
-            const int yy = y + (flip ? PAD - dy : dy - PAD);
-            if ((unsigned)yy >= (unsigned)H) continue;
-            for (int dx = 0; dx < K; ++dx) {
-                const int xx = x + (flip ? PAD - dx : dx - PAD);
-                if ((unsigned)xx >= (unsigned)W) continue;
-                const float* ip = in + ((size_t)(b * H + yy) * W + xx) * Cs;
-                for (int s = 0; s < Cs; ++s) acc = fmaf(ip[s], Wp[(size_t)((dy * K + dx) * Cs + s) * Cw + c], acc);
-            }
-        }
-        out[(size_t)pix * Cw + c] = acc;
-    }
-}
-
 // An nn.PReLU folded into the epilogue of the MFMA thin-input kernels (the same contract as IgemmArgs::act_*): y = also
 // write prelu(out) there (forward); x = the PReLU's input, the stored value becomes acc * (x > 0 ? 1 : slope) and the wave's
 // share of the slope gradient goes to part[(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave] (data gradient of a thin-OUTPUT layer).
@@ -629,6 +403,8 @@ int fg_launch_thin_in_conv(fg_ctx* ctx, const float* in, const float* Wp, const 
                            float* padbuf, long long padbuf_floats) {
     if (actf) actf->applied = 0;
     if (actb) actb->applied = 0;
+    auto refuse = [&]() { return fg_set_err(ctx, FG_ERR_INVALID, "thin_in: B=%d H=%d W=%d Cs=%d Cw=%d k=%d is no thin layer below 2^31 floats", B, H, W, Cs, Cw, k); };
+    if (!fg_thin_layer(Cs, Cw, k) || !fg_thin_fits(B, H, W, Cw)) return refuse();
     // profile label "thin_in<k,Cs>": algorithmic bytes = the thin input read once + the wide output written once (a fused PReLU
     // forward writes it twice, a fused PReLU backward also reads the PReLU's input)
     char plabel[48] = "";
@@ -653,12 +429,8 @@ int fg_launch_thin_in_conv(fg_ctx* ctx, const float* in, const float* Wp, const 
         return true;
     };
     auto armed = [&]() { if (epi.y) actf->applied = 1; if (epi.x) actb->applied = 1; };
-    if (Cw % 64) return fg_set_err(ctx, FG_ERR_INVALID, "thin_in: Cw %% 64");
-    const int cblk = Cw >= 256 ? 256 : Cw;
-    if (Cw % cblk || 256 % cblk) return fg_set_err(ctx, FG_ERR_INVALID, "thin_in: Cw=%d unsupported", Cw);
     const int npix = B * H * W;
     if (npix == 0) return FG_OK;
-    dim3 grid(fg_cdiv(npix, 128), Cw / cblk);
     if (k == 3 && (Cs == 1 || Cs == 3)) {
         int lgH = -1, lgW = -1;
         for (int q = 0; q < 15; ++q) { if ((1 << q) == H) lgH = q; if ((1 << q) == W) lgW = q; }
@@ -690,7 +462,7 @@ int fg_launch_thin_in_conv(fg_ctx* ctx, const float* in, const float* Wp, const 
         armed();
         return FG_OK;
     }
-    if ((k == 3 && Cs == 4) || ((k == 5 || k == 7) && (Cs == 1 || Cs == 3))) {      // exactly the TIL(...) instances below
+    {   // what fg_thin_layer leaves: 3x3 at Cs = 4, 5x5 / 7x7 at Cs = 1 | 3 -- exactly the TIL(...) instances below
         int lgH = -1, lgW = -1;
         for (int q = 0; q < 15; ++q) { if ((1 << q) == H) lgH = q; if ((1 << q) == W) lgW = q; }
         int nb = fg_cdiv(fg_cdiv(npix, 32), 4);
@@ -729,50 +501,7 @@ int fg_launch_thin_in_conv(fg_ctx* ctx, const float* in, const float* Wp, const 
         TIL(3, 4) TIL(5, 1) TIL(5, 3) TIL(7, 1) TIL(7, 3)
 #undef TIL
     }
-    if (k == 3 && (Cs == 1 || Cs == 3 || Cs == 4) && (Cw == 64 || Cw == 128)) {
-        dim3 rgrid(fg_cdiv(B * H, 4), 1);
-#define TIR3(CC, JJ)                                                                                                 \
-    if (Cs == CC && Cw == JJ * 64) {                                                                                 \
-        hipLaunchKernelGGL((thin_in_row3_kernel<CC, JJ>), rgrid, dim3(256), 0, ctx->stream, in, Wp, bias, out, B, H, W, \
-                           flip, Cw);                                                                                \
-        FG_CHECK_LAUNCH(ctx);                                                                                        \
-        return FG_OK;                                                                                                \
-    }
-        TIR3(1, 1) TIR3(3, 1) TIR3(4, 1) TIR3(1, 2) TIR3(3, 2) TIR3(4, 2)
-#undef TIR3
-    }
-    {
-        int nblk = fg_cdiv(npix, 4);
-        if (nblk > 4096) nblk = 4096;
-#define TI(KK, CC, JJ)                                                                                               \
-    if (k == KK && Cs == CC && Cw % (JJ * 64) == 0 && (JJ == 1 || Cw == JJ * 64)) {                                 \
-        hipLaunchKernelGGL((thin_in_kernel<KK, CC, JJ>), dim3(nblk, Cw / (JJ * 64)), dim3(256), 0, ctx->stream, in, Wp, \
-                           bias, out, B, H, W, flip, Cw);                                                           \
-        FG_CHECK_LAUNCH(ctx);                                                                                       \
-        return FG_OK;                                                                                               \
-    }
-        TI(3, 1, 2) TI(3, 3, 2) TI(3, 4, 2) TI(3, 1, 1) TI(3, 3, 1) TI(3, 4, 1)
-    }
-    if ((k == 5 || k == 7) && (Cs == 1 || Cs == 3)) {
-        const int pad = (k - 1) / 2;
-        const int wp = (W + 2 * pad + 3) / 4 * 4 + 4;
-        const size_t lds = (size_t)(4 + 2 * pad) * wp * Cs * sizeof(float) + 64;
-        dim3 rgrid(B * ((H + 3) / 4), Cw / 64);
-#define TIR(KK, CC)                                                                                                  \
-    if (k == KK && Cs == CC) {                                                                                       \
-        hipLaunchKernelGGL((thin_in_rows_kernel<KK, CC>), rgrid, dim3(256), lds, ctx->stream, in, Wp, bias, out, B, H, W, \
-                           flip, Cw);                                                                                \
-        FG_CHECK_LAUNCH(ctx);                                                                                        \
-        return FG_OK;                                                                                                \
-    }
-        TIR(5, 1) TIR(5, 3) TIR(7, 1) TIR(7, 3)
-#undef TIR
-    }
-#undef TI
-    hipLaunchKernelGGL(thin_in_generic_kernel, grid, dim3(256), 0, ctx->stream, in, Wp, bias, out, B, H, W, Cs, Cw, k,
-                       flip, cblk);
-    FG_CHECK_LAUNCH(ctx);
-    return FG_OK;
+    return refuse();
 }
 
 // ---------------------------------------------------------------------------------
@@ -1238,24 +967,25 @@ __global__ __launch_bounds__(256) void thin_out_rows_gather_kernel(const float* 
 
 int fg_launch_thin_out_conv(fg_ctx* ctx, const float* in, const float* Wp, const float* bias, float* out, int B, int H,
                             int W, int Cw, int Cs, int k, int flip, int sigmoid, float* rbuf, long long rbuf_floats) {
-    if (Cs > 4) return fg_set_err(ctx, FG_ERR_INVALID, "thin_out: Cs > 4");
+    auto refuse = [&]() { return fg_set_err(ctx, FG_ERR_INVALID, "thin_out: B=%d H=%d W=%d Cs=%d Cw=%d k=%d is no thin layer below 2^31 floats", B, H, W, Cs, Cw, k); };
+    if (!fg_thin_layer(Cs, Cw, k) || !fg_thin_fits(B, H, W, Cw)) return refuse();
     const int npix = B * H * W;
     if (npix == 0) return FG_OK;
     // profile label "thin_out<k,Cs>": algorithmic bytes = the wide input read once + the thin output written once
     char plabel[48] = "";
     if (ctx->prof) snprintf(plabel, sizeof(plabel), "thin_out<%d,%d>", k, Cs);
     FgProfScope prof(ctx, fg_intern(ctx, plabel), 2.0 * npix * (double)k * k * Cs * Cw, 0.0, 4.0 * npix * ((double)Cw + Cs));
-    if (rbuf && !flip && (k == 5 || k == 7) && (Cs == 1 || Cs == 3) && Cw % 32 == 0 && (long long)npix * 32 <= rbuf_floats) {
+    if (rbuf && !flip && (k == 5 || k == 7) && (long long)npix * 32 <= rbuf_floats) {
         dim3 grid(B * ((H + 3) / 4) * ((W + 31) / 32));
+        // (attr_key, here and in TOS / TOT: one key per macro expansion = per template instance; the "limit raised" flag lives in the
+        // context, i.e. per device, like every other launcher's -- fg_attr_first)
 #define TOR(KK, CC)                                                                                                  \
         if (k == KK && Cs == CC) {                                                                                   \
             const size_t lds = (size_t)((4 + KK - 1) * 32 * 36 + KK * 32 * 33) * sizeof(float);                      \
-            static bool attr = false;                                                                                \
-            if (!attr) {                                                                                             \
+            static char attr_key;                                                                                    \
+            if (fg_attr_first(ctx, &attr_key))                                                                       \
                 FG_HIP(ctx, hipFuncSetAttribute((const void*)thin_out_rows_mfma_kernel<KK, CC>,                      \
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));              \
-                attr = true;                                                                                         \
-            }                                                                                                        \
             hipLaunchKernelGGL((thin_out_rows_mfma_kernel<KK, CC>), grid, dim3(256), lds, ctx->stream, in, Wp, rbuf, B, H, W, Cw); \
             FG_CHECK_LAUNCH(ctx);                                                                                    \
             hipLaunchKernelGGL((thin_out_rows_gather_kernel<KK, CC>), dim3(fg_cdiv(npix * CC, 256)), dim3(256), 0,    \
@@ -1266,7 +996,6 @@ int fg_launch_thin_out_conv(fg_ctx* ctx, const float* in, const float* Wp, const
         TOR(5, 1) TOR(5, 3) TOR(7, 1) TOR(7, 3)
 #undef TOR
     }
-    dim3 grid(fg_cdiv(npix, 64));
     const long long in_bytes = (long long)npix * Cw * 4;
     {   // 3x3 on the matrix pipe (fg_set_fusion bit FG_FUSE_THIN_SLAB; off: the sliding-window VALU kernel)
         const bool use_slab = (ctx->fusion & FG_FUSE_THIN_SLAB) != 0;
@@ -1292,12 +1021,10 @@ int fg_launch_thin_out_conv(fg_ctx* ctx, const float* in, const float* Wp, const
             const size_t lds = (size_t)(R + 2) * W * 29 * sizeof(float);
 #define TOS(JJ, CC)                                                                                                  \
             if (Cw == JJ * 64 && Cs == CC) {                                                                         \
-                static bool attr = false;                                                                            \
-                if (!attr) {                                                                                         \
+                static char attr_key;                                                                                \
+                if (fg_attr_first(ctx, &attr_key))                                                                   \
                     FG_HIP(ctx, hipFuncSetAttribute((const void*)thin_out_slab_mfma_kernel<JJ, CC>,                  \
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));        \
-                    attr = true;                                                                                     \
-                }                                                                                                    \
                 hipLaunchKernelGGL((thin_out_slab_mfma_kernel<JJ, CC>), dim3(nblk), dim3(256), lds, ctx->stream, in, Wp, bias, \
                                    out, H, W, R, flip, sigmoid, (int)in_bytes);                                      \
                 FG_CHECK_LAUNCH(ctx);                                                                                \
@@ -1333,18 +1060,22 @@ int fg_launch_thin_out_conv(fg_ctx* ctx, const float* in, const float* Wp, const
         TO(3, 1, 1) TO(3, 1, 3) TO(3, 2, 1) TO(3, 2, 3)
     }
 #undef TO
-    if (Cw % 32 == 0 && (k == 3 || k == 5 || k == 7) && (Cs == 1 || Cs == 3)) {
+    if (Cs == 4) {      // 3x3 only (fg_thin_layer); no instance above holds Cs = 4
+        hipLaunchKernelGGL(thin_out_generic_kernel, dim3(fg_cdiv(npix, 64)), dim3(256), 0, ctx->stream, in, Wp, bias, out, B, H, W, Cw, Cs, k,
+                           flip, sigmoid);
+        FG_CHECK_LAUNCH(ctx);
+        return FG_OK;
+    }
+    {
         const int tp = 16 + k - 1;
         const size_t lds = (size_t)tp * tp * 36 * sizeof(float);
         dim3 tgrid(B * ((H + 15) / 16) * ((W + 15) / 16));
 #define TOT(KK, CC)                                                                                                  \
     if (k == KK && Cs == CC) {                                                                                       \
-        static bool attr = false;                                                                                    \
-        if (!attr) {                                                                                                 \
+        static char attr_key;                                                                                        \
+        if (fg_attr_first(ctx, &attr_key))                                                                           \
             FG_HIP(ctx, hipFuncSetAttribute((const void*)thin_out_tiled_kernel<KK, CC>,                              \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
-            attr = true;                                                                                             \
-        }                                                                                                            \
         hipLaunchKernelGGL((thin_out_tiled_kernel<KK, CC>), tgrid, dim3(256), lds, ctx->stream, in, Wp, bias, out, B, H, \
                            W, Cw, flip, sigmoid);                                                                    \
         FG_CHECK_LAUNCH(ctx);                                                                                        \
@@ -1353,102 +1084,18 @@ int fg_launch_thin_out_conv(fg_ctx* ctx, const float* in, const float* Wp, const
         TOT(3, 1) TOT(3, 3) TOT(5, 1) TOT(5, 3) TOT(7, 1) TOT(7, 3)
 #undef TOT
     }
-    hipLaunchKernelGGL(thin_out_generic_kernel, grid, dim3(256), 0, ctx->stream, in, Wp, bias, out, B, H, W, Cw, Cs, k,
-                       flip, sigmoid);
-    FG_CHECK_LAUNCH(ctx);
-    return FG_OK;
+    return refuse();
 }
 
 // ---------------------------------------------------------------------------------
 // thin wgrad: gw[tap][s][c] = sum_pix thin[pix + sgn*off(tap)][s] * wide[pix][c]
 // ---------------------------------------------------------------------------------
 #define TW_BLOCKS FG_THIN_WGRAD_BLOCKS
-#define TW_ROWS 4   // image rows per staged strip
-// Block = cblk wide channels x PL pixel lanes.  A strip of TW_ROWS image rows of the THIN operand (+ halo, zero
-// padded) is staged in LDS, so the 27 thin reads per pixel are conflict-free LDS broadcasts without bounds checks;
-// the wide operand streams from HBM, coalesced over channels.  Strips are distributed grid-stride; every block
-// writes one partial [taps*CS][Cw] slab, reduced by colsum_final_kernel (fp64).
-template <int K, int CS>
-__global__ __launch_bounds__(256) void thin_wgrad_kernel(const float* __restrict__ thin, const float* __restrict__ wide,
-                                                         float* __restrict__ part, int B, int H, int W, int Cw, int sgn,
-                                                         int cblk) {
-    constexpr int PAD = (K - 1) / 2;
-    constexpr int NA = K * K * CS;
-    extern __shared__ float sh[];
-    const int WP = W + 2 * PAD;
-    float* tile = sh;                                  // [(TW_ROWS + 2 PAD)][WP][CS]
-    float* red = sh + (TW_ROWS + 2 * PAD) * WP * CS;   // [PL][NA][cblk] (PL > 1 only)
-    const int pl = threadIdx.x / cblk, tc = threadIdx.x - pl * cblk;
-    const int PL = 256 / cblk;
-    const int c = blockIdx.y * cblk + tc;
-    const int strips_per_img = (H + TW_ROWS - 1) / TW_ROWS;
-    const int nstrips = B * strips_per_img;
-    float acc[NA];
-#pragma unroll
-    for (int t = 0; t < NA; ++t) acc[t] = 0.f;
-    for (int st = blockIdx.x; st < nstrips; st += gridDim.x) {
-        const int b = st / strips_per_img, y0 = (st - b * strips_per_img) * TW_ROWS;
-        __syncthreads();
-        for (int i = threadIdx.x; i < (TW_ROWS + 2 * PAD) * WP * CS; i += 256) {
-            const int s = i % CS;
-            const int t = i / CS;
-            const int xx = t % WP - PAD, yy = y0 + t / WP - PAD;
-            float v = 0.f;
-            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) v = thin[((size_t)(b * H + yy) * W + xx) * CS + s];
-            tile[i] = v;
-        }
-        __syncthreads();
-        const int rows = min(TW_ROWS, H - y0);
-        const int npx = rows * W;
-        for (int j0 = pl; j0 < npx; j0 += 4 * PL) {
-            float wv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {      // 4 independent coalesced loads in flight
-                const int j = j0 + u * PL;
-                wv[u] = j < npx ? wide[((size_t)(b * H + y0) * W + j) * Cw + c] : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + u * PL;
-                if (j >= npx) break;
-                const int ry = j / W, rx = j - ry * W;
-#pragma unroll
-                for (int dy = 0; dy < K; ++dy)
-#pragma unroll
-                    for (int dx = 0; dx < K; ++dx) {
-                        const float* tp = tile + ((ry + PAD + sgn * (dy - PAD)) * WP + rx + PAD + sgn * (dx - PAD)) * CS;
-#pragma unroll
-                        for (int s = 0; s < CS; ++s)
-                            acc[(dy * K + dx) * CS + s] = fmaf(tp[s], wv[u], acc[(dy * K + dx) * CS + s]);
-                    }
-            }
-        }
-    }
-    float* dst = part + (size_t)blockIdx.x * NA * Cw;
-    if (PL == 1) {
-#pragma unroll
-        for (int t = 0; t < NA; ++t) dst[(size_t)t * Cw + c] = acc[t];
-    } else {
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < NA; ++t) red[(pl * NA + t) * cblk + tc] = acc[t];
-        __syncthreads();
-        if (pl == 0) {
-#pragma unroll
-            for (int t = 0; t < NA; ++t) {
-                float s = 0.f;
-                for (int q = 0; q < PL; ++q) s += red[(q * NA + t) * cblk + tc];
-                dst[(size_t)t * Cw + c] = s;
-            }
-        }
-    }
-}
-
 // 3x3 thin weight gradient on the fp32 matrix pipe: gw[(tap,s)][c] = sum_pix thin[pix + sgn*(tap - 1)][s] * wide[pix][c].
 // One v_mfma_f32_32x32x2_f32 per pixel PAIR and 32 wide channels: A = wide[pix][c] straight from global (every element is
 // used exactly once, so there is nothing to stage), B = the <= 27 shifted thin values of the pair (a per-lane gather from
-// the tiny thin tensor, zero outside the image), columns 27..31 idle.  The VALU kernel above needs one LDS read per FMA
-// and ran 10x over the HBM time of its 33 MB stream.
+// the tiny thin tensor, zero outside the image), columns 27..31 idle.  (The VALU kernel it replaced needed one LDS read per
+// FMA and ran 10x over the HBM time of its 33 MB stream.)
 // PADDED (5x5 / 7x7 layers, power-of-two maps): `thin` is the zero-bordered copy above, so a shifted value is ONE add (pixel base +
 // per-lane constant) and ONE load -- no bounds, no select (the 5 gathers of a 7x7x3 pixel pair cost ~50 VALU instructions per 10
 // MFMAs before, and every instruction issued beside an MFMA costs its pipe 6-9 cycles: DESIGN 4.7); columns >= NA read tap 0 and are
@@ -1593,16 +1240,18 @@ __global__ __launch_bounds__(256) void thin_wgrad_mfma_kernel(const float* __res
 }
 
 // wide_colsum (optional): receives sum_pix wide[pix][c] (beta = 0) from the ones column of the matrix-pipe kernels; *colsum_done
-// tells the caller whether it was produced (the VALU fallback kernels do not).  With it the slabs have k*k*Cs + 1 rows: `scratch`
+// tells the caller whether it was produced (3x3 layers with FG_FUSE_THIN_BIAS set).  With it the slabs have k*k*Cs + 1 rows: `scratch`
 // holds FG_THIN_WGRAD_BLOCKS * (k*k*Cs + 1) * Cw floats for them.
-// gradW_ref / unpack_mode (optional, matrix-pipe kernels only; *unpacked = 1 when used): the final sum writes the reference layout
+// gradW_ref / unpack_mode (optional; *unpacked = 1 when used): the final sum writes the reference layout
 // gradW[O][I][k][k] itself (beta = 0) instead of gw_tsc -- no thin_unpack_grad launch behind it
 int fg_launch_thin_wgrad(fg_ctx* ctx, const float* thin, const float* wide, float* gw_tsc, int B, int H, int W, int Cs,
                          int Cw, int k, int shift_thin, float* scratch, float* wide_colsum, int* colsum_done, float* gradW_ref,
                          int unpack_mode, int* unpacked) {
     if (colsum_done) *colsum_done = 0;
     if (unpacked) *unpacked = 0;
-    if (Cw % 64) return fg_set_err(ctx, FG_ERR_INVALID, "thin_wgrad: Cw %% 64");
+    // (32-bit pixel * channel indices in the kernels: fg_thin_fits is a precondition, like the layer predicate)
+    auto refuse = [&]() { return fg_set_err(ctx, FG_ERR_INVALID, "thin_wgrad: B=%d H=%d W=%d Cs=%d Cw=%d k=%d is no thin layer below 2^31 floats", B, H, W, Cs, Cw, k); };
+    if (!fg_thin_layer(Cs, Cw, k) || !fg_thin_fits(B, H, W, Cw)) return refuse();
     // (3x3 layers only: the thin-INPUT convolutions of models.lua:385 / models_c2f.lua:123, 244)
     const int ones = (wide_colsum && colsum_done && k == 3 && (ctx->fusion & FG_FUSE_THIN_BIAS)) ? 1 : 0;      // fg_set_fusion
     const int NR = k * k * Cs + ones;
@@ -1621,70 +1270,48 @@ int fg_launch_thin_wgrad(fg_ctx* ctx, const float* thin, const float* wide, floa
     char plabel[48] = "";
     if (ctx->prof) snprintf(plabel, sizeof(plabel), "thin_wgrad<%d,%d>", k, Cs);
     FgProfScope prof(ctx, fg_intern(ctx, plabel), 2.0 * B * H * W * (double)k * k * Cs * Cw, 0.0, 4.0 * B * H * W * ((double)Cw + Cs));
-    {
-        const long long npairs = ((long long)B * H * W + 1) / 2;
-        int nb = (int)((npairs + 3) / 4 < TW_BLOCKS ? (npairs + 3) / 4 : TW_BLOCKS);
-        if (nb < 1) nb = 1;
-        dim3 grid(nb, Cw / 64);
-        int lgH = -1, lgW = -1;
-        for (int q = 0; q < 15; ++q) { if ((1 << q) == H) lgH = q; if ((1 << q) == W) lgW = q; }
-        const bool fits = (long long)B * H * W * Cw < (1LL << 31);
-        // 5x5 / 7x7 on power-of-two maps: gather from a zero-bordered copy of the thin tensor kept in the tail of the slab area
-        // (the layer's slabs are large: the copy displaces a few of the TW_BLOCKS blocks)
-        if (fits && k >= 5 && lgH >= 0 && lgW >= 0 && (Cs == 1 || Cs == 3)) {
-            const int pad = (k - 1) / 2;
-            const long long slab = (long long)NR * Cw, padf = (long long)B * (H + 2 * pad) * (W + 2 * pad) * Cs;
-            const long long take = (padf + slab - 1) / slab;
-            if (take <= TW_BLOCKS / 4 && padf < (1LL << 28) && (long long)B * H * W * Cw * 4 < 0x7FFFFFF0LL) {
-                const int nbp = nb < TW_BLOCKS - (int)take ? nb : TW_BLOCKS - (int)take;
-                float* padded = scratch + (long long)(TW_BLOCKS - take) * slab;
-{ const int rcp = fg_launch_thin_pad(ctx, thin, padded, B, H, W, Cs, pad); if (rcp) return rcp; }
-                dim3 gridp(nbp, Cw / 64);
-#define TWP(KK, CC)                                                                                                  \
-                if (k == KK && Cs == CC) {                                                                           \
-                    hipLaunchKernelGGL((thin_wgrad_mfma_kernel<KK, CC, 1>), gridp, dim3(256), 0, ctx->stream, padded, wide, scratch, B, \
-                                       H, W, Cw, shift_thin, lgH, lgW);                                              \
-                    FG_CHECK_LAUNCH(ctx);                                                                            \
-                    return finish(nbp);                                                                              \
-                }
-                TWP(5, 1) TWP(5, 3) TWP(7, 1) TWP(7, 3)
-#undef TWP
-            }
-        }
-#define TWM(KK, CC)                                                                                                  \
-        if (fits && k == KK && Cs == CC) {                                                                           \
-            if (KK == 3 && ones)                                                                                     \
-                hipLaunchKernelGGL((thin_wgrad_mfma_kernel<KK, CC, 0, (KK == 3 ? 1 : 0)>), grid, dim3(256), 0, ctx->stream, thin, wide, \
-                                   scratch, B, H, W, Cw, shift_thin, lgH, lgW);                                      \
-            else                                                                                                     \
-                hipLaunchKernelGGL((thin_wgrad_mfma_kernel<KK, CC>), grid, dim3(256), 0, ctx->stream, thin, wide, scratch, B, H, \
-                                   W, Cw, shift_thin, lgH, lgW);                                                     \
-            FG_CHECK_LAUNCH(ctx);                                                                                    \
-            return finish(nb);                                                                                       \
-        }
-        TWM(3, 1) TWM(3, 3) TWM(3, 4) TWM(5, 1) TWM(5, 3) TWM(7, 1) TWM(7, 3)
-#undef TWM
-    }
-    const int cblk = Cw >= 256 ? 256 : Cw;
-    if (Cw % cblk || 256 % cblk) return fg_set_err(ctx, FG_ERR_INVALID, "thin_wgrad: Cw=%d unsupported", Cw);
-    const int nstrips = B * ((H + TW_ROWS - 1) / TW_ROWS);
-    int nb = nstrips < TW_BLOCKS ? nstrips : TW_BLOCKS;
+    const long long npairs = ((long long)B * H * W + 1) / 2;
+    int nb = (int)((npairs + 3) / 4 < TW_BLOCKS ? (npairs + 3) / 4 : TW_BLOCKS);
     if (nb < 1) nb = 1;
-    const int PL = 256 / cblk;
-    const int NA = k * k * Cs;
-    const int pad = (k - 1) / 2;
-    dim3 grid(nb, Cw / cblk);
-    const size_t lds = ((size_t)(TW_ROWS + 2 * pad) * (W + 2 * pad) * Cs + (PL > 1 ? (size_t)PL * NA * cblk : 0)) * sizeof(float);
-#define TWG(KK, CC)                                                                                                  \
-    if (k == KK && Cs == CC) {                                                                                       \
-        hipLaunchKernelGGL((thin_wgrad_kernel<KK, CC>), grid, dim3(256), lds, ctx->stream, thin, wide, scratch, B, H, W, \
-                           Cw, shift_thin, cblk);                                                                    \
-        FG_CHECK_LAUNCH(ctx);                                                                                        \
-        return fg_launch_colsum_final(ctx, scratch, nb, NA * Cw, 0.f, gw_tsc);                                       \
+    dim3 grid(nb, Cw / 64);
+    int lgH = -1, lgW = -1;
+    for (int q = 0; q < 15; ++q) { if ((1 << q) == H) lgH = q; if ((1 << q) == W) lgW = q; }
+    // 5x5 / 7x7 on power-of-two maps: gather from a zero-bordered copy of the thin tensor kept in the tail of the slab area
+    // (the layer's slabs are large: the copy displaces a few of the TW_BLOCKS blocks)
+    if (k >= 5 && lgH >= 0 && lgW >= 0) {
+        const int pad = (k - 1) / 2;
+        const long long slab = (long long)NR * Cw, padf = (long long)B * (H + 2 * pad) * (W + 2 * pad) * Cs;
+        const long long take = (padf + slab - 1) / slab;
+        if (take <= TW_BLOCKS / 4 && padf < (1LL << 28) && (long long)B * H * W * Cw * 4 < 0x7FFFFFF0LL) {
+            const int nbp = nb < TW_BLOCKS - (int)take ? nb : TW_BLOCKS - (int)take;
+            float* padded = scratch + (long long)(TW_BLOCKS - take) * slab;
+            { const int rcp = fg_launch_thin_pad(ctx, thin, padded, B, H, W, Cs, pad); if (rcp) return rcp; }
+            dim3 gridp(nbp, Cw / 64);
+#define TWP(KK, CC)                                                                                                  \
+            if (k == KK && Cs == CC) {                                                                               \
+                hipLaunchKernelGGL((thin_wgrad_mfma_kernel<KK, CC, 1>), gridp, dim3(256), 0, ctx->stream, padded, wide, scratch, B, \
+                                   H, W, Cw, shift_thin, lgH, lgW);                                                  \
+                FG_CHECK_LAUNCH(ctx);                                                                                \
+                return finish(nbp);                                                                                  \
+            }
+            TWP(5, 1) TWP(5, 3) TWP(7, 1) TWP(7, 3)
+#undef TWP
+        }
     }
-    TWG(3, 1) TWG(3, 3) TWG(3, 4) TWG(5, 3) TWG(7, 3) TWG(7, 1)
-#undef TWG
-    return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "thin_wgrad: k=%d Cs=%d not built", k, Cs);
+#define TWM(KK, CC)                                                                                                  \
+    if (k == KK && Cs == CC) {                                                                                       \
+        if (KK == 3 && ones)                                                                                         \
+            hipLaunchKernelGGL((thin_wgrad_mfma_kernel<KK, CC, 0, (KK == 3 ? 1 : 0)>), grid, dim3(256), 0, ctx->stream, thin, wide, \
+                               scratch, B, H, W, Cw, shift_thin, lgH, lgW);                                          \
+        else                                                                                                         \
+            hipLaunchKernelGGL((thin_wgrad_mfma_kernel<KK, CC>), grid, dim3(256), 0, ctx->stream, thin, wide, scratch, B, H, \
+                               W, Cw, shift_thin, lgH, lgW);                                                         \
+        FG_CHECK_LAUNCH(ctx);                                                                                        \
+        return finish(nb);                                                                                           \
+    }
+    TWM(3, 1) TWM(3, 3) TWM(3, 4) TWM(5, 1) TWM(5, 3) TWM(7, 1) TWM(7, 3)
+#undef TWM
+    return refuse();
 }
 
 // ---------------------------------------------------------------------------------

@@ -442,7 +442,10 @@ int fg_c2f_coarse_diff(fg_ctx* ctx, const float* fine, float* coarse, float* dif
  * all three.  Refused (FG_ERR_UNSUPPORTED) are only, with upsample2x = 1 (the folded nearest-x2 upsample):
  *   - k = 7 (the folded window needs more tap groups than the kernels hold), and
  *   - a THIN layer: 1 or 3 channels on one side (also 4 at k = 3) against 64, 128 or a multiple of 256 on the other.  Those layers
- *     have kernels of their own (the image-side convolutions of the models), without a folded form.
+ *     have kernels of their own (the image-side convolutions of the models), without a folded form;
+ * and, with either value of upsample2x:
+ *   - a THIN layer whose wide operand, batch * h * w * max(cin, cout), has 2^31 floats (8 GiB) or more: its kernels index that
+ *     operand with 32 bits.  Nothing is launched; fg_net_forward refuses such a layer of a net at that batch, naming the layer.
  * Every other layer with few channels on one side (2 channels; 4 at 5x5 / 7x7; widths such as 192 or 320) is an ordinary
  * convolution on zero-padded channel rows.  fg_net_create classifies a FG_CONV layer the same way.
  * Linear(in_f -> 1) runs as a matrix-vector product at any batch. */

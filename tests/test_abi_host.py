@@ -86,6 +86,17 @@ def test_default_library_has_no_ab_switches(lib):
     assert readers == ["api.hip", "step.hip"], readers
 
 
+def test_lds_limits_are_raised_per_context_not_per_process():
+    """A kernel's dynamic-LDS limit is a property of the device: a launcher that remembers "already raised" in a process-wide
+    `static bool attr` skips it on a second context bound to another device.  Every site asks fg_attr_first(ctx, &attr_key)."""
+    csrc = os.path.join(ROOT, "face_generator_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".hip"):
+            src = open(os.path.join(csrc, f)).read()
+            assert not re.search(r"static\s+bool\s+attr\b", src), f
+            assert src.count("hipFuncSetAttribute(") == 0 or "fg_attr_first(" in src, f
+
+
 def test_no_gpu_fails_loudly_not_silently(lib):
     if torch.cuda.is_available():
         pytest.skip("GPU present")

@@ -84,8 +84,9 @@ def test_the_new_cases_take_the_signatures_written_next_to_them(audit):
 
 def test_the_three_conv_passes_accept_the_same_geometries(audit):
     """(b) forward, data gradient and weight gradient all run or all return the same code; fg_conv2d_workspace_bytes is enough for
-    the ones that run (the entries got exactly that many bytes); odd k <= 7 with 'same' padding is refused only for the two
-    reasons include/facegen_hip.h states: the folded upsample on a thin layer, and the folded upsample at 7x7."""
+    the ones that run (the entries got exactly that many bytes); odd k <= 7 with 'same' padding is refused only for the three
+    reasons include/facegen_hip.h states: the folded upsample on a thin layer, the folded upsample at 7x7, and a thin layer whose
+    wide operand has 2^31 floats or more (beyond the sweep's cap of 2^25: test_thin_layers_of_2_31_floats_are_refused_by_all_three_passes)."""
     bad = []
     for j in audit["sweep"]:
         codes = {p: j["rc"][p][0] for p in A.PASSES}
@@ -99,6 +100,52 @@ def test_the_three_conv_passes_accept_the_same_geometries(audit):
         if any(c != want for c in codes.values()):
             bad.append((j["shape"], j["math"], j["fusion"], {p: j["rc"][p] for p in A.PASSES}))
     assert not bad, "%d geometries; first: %s" % (len(bad), bad[:5])
+
+
+SIZE_RULE = A.ENGINE + r"""
+import ctypes
+from face_generator_amd.runtime import make_specs
+for j in json.load(open(sys.argv[1])): run_abi(j)
+# a net knows its batch when it runs, not when it is created: one thin layer, bound to a small buffer nobody dereferences
+h, off, buf = ctypes.c_void_p(), ctypes.c_longlong(), torch.empty(4096)
+ctx.check(lib.fg_net_create(ctx.h, make_specs([("CONV", 3, 64, 3, 1)]), 1, 3, 512, 512, ctypes.byref(h)))
+ctx.check(lib.fg_net_bind(h, buf.data_ptr(), buf.data_ptr(), buf.data_ptr()))
+nb = lib.fg_net_workspace_bytes(h, 127)
+for B in (128, 127):
+    say("fg-job " + json.dumps(dict(kind="net", shape=[B])))
+    say("fg-pass fwd")
+    rc = lib.fg_net_forward(h, B, buf.data_ptr(), buf.data_ptr(), nb, 0, None, 0, ctypes.byref(off))
+    say("fg-rc %%d %%s" %% (rc, lib.fg_last_error(ctx.h).decode() if rc else ""))
+"""
+AT_2_31 = [(128, 512, 512, 3, 64, 3), (128, 512, 512, 64, 1, 5), (128, 512, 512, 1, 64, 7), (32, 512, 512, 256, 3, 3)]
+
+
+def test_thin_layers_of_2_31_floats_are_refused_by_all_three_passes(tmp_path):
+    """The size rule (csrc/fg_internal.h fg_thin_fits), planning-only through the C entries: a thin layer whose wide operand has
+    exactly 2^31 floats gets FG_ERR_UNSUPPORTED with one message from forward, data gradient and weight gradient and launches
+    nothing (before the rule, 64 -> 1 at 5x5 ran forward and data gradient and was refused in the weight gradient alone); one
+    sample fewer and all three run, the weight gradient on the matrix pipe.  A net with such a first layer is refused by
+    fg_net_forward at batch 128, naming layer 0, and runs at batch 127."""
+    import json
+    t0 = time.time()
+    shapes = AT_2_31 + [(s[0] - 1,) + s[1:] for s in AT_2_31]
+    assert all(b * h * w * max(ci, co) == 2 ** 31 for b, h, w, ci, co, k in AT_2_31)
+    jobs = [dict(list="size-rule", kind="conv", shape=list(s) + [0], math=0, fusion=A.FG_FUSE_DEFAULT, passes=list(A.PASSES)) for s in shapes]
+    f = tmp_path / "jobs.json"
+    f.write_text(json.dumps(jobs))
+    got = A.parse_jobs(A._run(SIZE_RULE, [str(f)]))
+    assert len(got) == len(shapes) + 2
+    for j in got[:4]:
+        assert {j["rc"][p][0] for p in A.PASSES} == {-4}, (j["shape"], j["rc"])          # FG_ERR_UNSUPPORTED
+        assert len({j["rc"][p][1] for p in A.PASSES}) == 1 and "2^31" in j["rc"]["fwd"][1], (j["shape"], j["rc"])
+        assert not any(j["sigs"].values()), (j["shape"], j["sigs"])
+    for j in got[4:8]:
+        assert all(j["rc"][p] == (0, "") for p in A.PASSES), (j["shape"], j["rc"])
+        assert any(s[0].startswith("(thin_wgrad_mfma_kernel<") for s in j["sigs"]["wgrad"]), (j["shape"], j["sigs"]["wgrad"])
+    at128, at127 = got[8:]
+    assert at128["rc"]["fwd"][0] == -4 and "layer 0" in at128["rc"]["fwd"][1] and not at128["sigs"]["fwd"], at128
+    assert at127["rc"]["fwd"] == (0, "") and any(s[0].startswith("(thin_in_mfma_kernel<3,") for s in at127["sigs"]["fwd"]), at127
+    assert time.time() - t0 < 30
 
 
 def test_nets_with_reclassified_layers_plan_and_run_forward_and_backward():
