@@ -1539,23 +1539,40 @@ int fg_launch_add_halves(fg_ctx* ctx, const float* a0, const float* b0, const fl
 }
 
 // stride-2 data gradient helper: out[b][2y][2x][c] = g[b][y][x][c], every other position 0 (out is [B][2H][2W][C])
+// V = 4: one float4 of C / 4 per element (C % 4 == 0, both operands on 16 bytes); V = 1: one float, any C.  CV = C / V, n = elements
+// of out.  FG_GRID caps the grid: the loop walks what lies above the cap.
+template <int V>
+__device__ __forceinline__ void zero_insert2_body(const float* __restrict__ g, float* __restrict__ out, int H, int W, int CV, long long n) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % CV);
+        long long t = i / CV;
+        const int X = (int)(t % (2 * W)); t /= 2 * W;
+        const int Y = (int)(t % (2 * H));
+        const long long b = t / (2 * H);
+        const bool live = ((X | Y) & 1) == 0;
+        const long long src = ((b * H + (Y >> 1)) * W + (X >> 1)) * CV + c;
+        if (V == 4) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (live) v = ((const float4*)g)[src];
+            ((float4*)out)[i] = v;
+        } else {
+            out[i] = live ? g[src] : 0.f;
+        }
+    }
+}
 __global__ void zero_insert2_kernel(const float* __restrict__ g, float* __restrict__ out, int H, int W, int C4, long long n4) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    const int c = (int)(i % C4);
-    long long t = i / C4;
-    const int X = (int)(t % (2 * W)); t /= 2 * W;
-    const int Y = (int)(t % (2 * H));
-    const long long b = t / (2 * H);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (((X | Y) & 1) == 0) v = ((const float4*)g)[((b * H + (Y >> 1)) * W + (X >> 1)) * C4 + c];
-    ((float4*)out)[i] = v;
+    zero_insert2_body<4>(g, out, H, W, C4, n4);
+}
+__global__ void zero_insert2_scalar_kernel(const float* __restrict__ g, float* __restrict__ out, int H, int W, int C, long long n) {
+    zero_insert2_body<1>(g, out, H, W, C, n);
 }
 int fg_launch_zero_insert2(fg_ctx* ctx, const float* g, float* out, int B, int H, int W, int C) {
-    if (C % 4) return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "zero_insert2: C %% 4");
-    const long long n4 = (long long)B * 2 * H * 2 * W * (C / 4);
-    if (n4 == 0) return FG_OK;
-    hipLaunchKernelGGL(zero_insert2_kernel, FG_GRID(n4, 256), dim3(256), 0, ctx->stream, g, out, H, W, C / 4, n4);
+    const bool v4 = C % 4 == 0 && (((uintptr_t)g | (uintptr_t)out) & 15) == 0;
+    const int CV = v4 ? C / 4 : C;
+    const long long n = (long long)B * 2 * H * 2 * W * CV;
+    if (n == 0) return FG_OK;
+    if (v4) hipLaunchKernelGGL(zero_insert2_kernel, FG_GRID(n, 256), dim3(256), 0, ctx->stream, g, out, H, W, CV, n);
+    else hipLaunchKernelGGL(zero_insert2_scalar_kernel, FG_GRID(n, 256), dim3(256), 0, ctx->stream, g, out, H, W, CV, n);
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }

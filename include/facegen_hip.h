@@ -153,6 +153,8 @@ enum fg_layer_type {
     FG_PRELU = 3,           /* nn.PReLU() -- one shared slope */
     FG_UPSAMPLE2X = 4,      /* nn.SpatialUpSamplingNearest(2) */
     FG_CONV = 5,            /* (cudnn|nn).SpatialConvolution(a=nIn, b=nOut, c=k, k, dW, dH, d=pad, pad); p = stride dW=dH (0/1: 1, 2: 2);
+                             * stride 2: odd k <= 7, pad (k - 1) / 2, even H and W (else FG_ERR_UNSUPPORTED from fg_net_create, naming
+                             * the layer), ANY channel counts -- forward, data gradient and parameter gradients all run;
                              * q = factor f of cudnn.SpatialConvolutionUpsample (0/1: none; f > 1: b = nOutputPlane * f * f planes, the
                              * NCHW output re-viewed as [b / f^2][H * f][W * f], layers/cudnnSpatialConvolutionUpsample.lua:14-31) */
     FG_BATCHNORM = 6,       /* nn.SpatialBatchNormalization(a=nF), p=eps, q=momentum */
@@ -254,7 +256,8 @@ int fg_bce_forward_backward(fg_ctx* ctx, const float* prob, const float* target,
 /* ---- optimizers on the flat vectors (interruptable_optimizers.lua:7-167) with the penalty and clamp of
  *      adversarial.lua:103-123 / 218-228 fused in:  g' = clamp(gscale*g + l1_mul*sign(p) + l2*p, +-clamp).
  *      Hyper-parameters are doubles (Lua numbers): 1-beta, the bias corrections and the step size are evaluated in
- *      double on the host exactly like interruptable_optimizers.lua:78-88, then rounded to fp32 once. ---- */
+ *      double on the host exactly like interruptable_optimizers.lua:78-88, then rounded to fp32 once.
+ *      Alignment: every vector (p, g, m, v, mom_buf, variance, g_out) needs 4 bytes only, at any n >= 0. ---- */
 int fg_adam_fused(fg_ctx* ctx, float* p, const float* g, float* m, float* v, long long n, float gscale, float l1_mul,
                   float l2, float clamp, double lr, double beta1, double beta2, double eps, int t, float* g_out);
 int fg_sgd_fused(fg_ctx* ctx, float* p, const float* g, float* mom_buf, long long n, float gscale, float l1_mul,

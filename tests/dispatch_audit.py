@@ -1,7 +1,9 @@
 """Which kernel does the library launch for which geometry?  Answered on the CPU: a planning-only context (get_context(-1)) with
 FG_LAUNCH_LOG=1 prints one line per launch, produced by the very host code that decides the launches on a device.  This module
-holds the three child programs (replay of the GPU parity lists, the seeded sweep of the public conv / linear entries, one training
-iteration of the baseline nets), the parser of their logs and the census of the launch sites in csrc/*.hip.
+holds the child programs (replay of the GPU parity lists, the seeded sweep of the public conv / linear entries, one training
+iteration of the baseline nets; the strided sweep and replay of one-layer stride-2 nets; the replay of the module-level pointwise,
+BatchNorm, optimizer and RNG lists), the parser of their logs, the census of the launch sites in csrc/*.hip and the census of the
+launches with a capped grid.
 tests/test_dispatch_coverage_host.py asserts on what they return; tests/DISPATCH_COVERAGE.md is the ledger.
 
 A launch's SIGNATURE is (launch-site text, block size, dynamic LDS bytes); the grid is left out.
@@ -104,6 +106,73 @@ def run_abi(job):
         say("fg-pass " + q)
         rc = calls[q]()
         say("fg-rc %%d %%s" %% (rc, lib.fg_last_error(ctx.h).decode() if rc else ""))
+"""
+
+# one-layer nets [FG_CONV p=2]: the only public way to a strided convolution.  Passes: create, fwd (train), bwd (both flags); the
+# workspace is exactly fg_net_workspace_bytes long
+STRIDED_ENGINE = ENGINE + r"""
+import ctypes
+from face_generator_amd.runtime import make_specs
+def run_strided(job):
+    settings(job)                       # the fusion bits are read when a net is created
+    say("fg-job " + json.dumps(job))
+    B, H, W, cin, cout, k = job["shape"]
+    h, off = ctypes.c_void_p(), ctypes.c_longlong()
+    def done(rc):
+        say("fg-rc %%d %%s" %% (rc, lib.fg_last_error(ctx.h).decode() if rc else ""))
+        return rc
+    say("fg-pass create")
+    if done(lib.fg_net_create(ctx.h, make_specs([("CONV", cin, cout, k, (k - 1) // 2, 2)]), 1, cin, H, W, ctypes.byref(h))):
+        return
+    n = lib.fg_net_num_params(h)
+    params, grads, buffers = torch.zeros(n), torch.zeros(n), torch.zeros(1)
+    ctx.check(lib.fg_net_bind(h, params.data_ptr(), grads.data_ptr(), buffers.data_ptr()))
+    nb = lib.fg_net_workspace_bytes(h, B)
+    ws, x, gy = torch.empty((nb + 3) // 4 + 1), torch.empty(B * H * W * cin), torch.empty(B * (H // 2) * (W // 2) * cout)
+    gx = torch.empty(x.numel())
+    say("fg-pass fwd")
+    done(lib.fg_net_forward(h, B, x.data_ptr(), ws.data_ptr(), nb, 1, None, 0, ctypes.byref(off)))
+    say("fg-pass bwd")
+    done(lib.fg_net_backward_range(h, B, x.data_ptr(), gy.data_ptr(), ws.data_ptr(), nb, 3, gx.data_ptr(), lib.fg_net_num_stages(h) - 1, 0))
+    lib.fg_net_destroy(h)
+"""
+
+STRIDED = STRIDED_ENGINE + r"""
+for j in json.load(open(sys.argv[1])): run_strided(j)
+"""
+
+STRIDED_REPLAY = STRIDED_ENGINE + r"""
+import test_gpu_strided_conv as TS
+for c in TS.STRIDED_CASES:
+    for m in ((0, 6) if c != TS.CAP_CASE else (0,)):
+        run_strided(dict(list="STRIDED_CASES", kind="sconv", shape=[int(v) for v in c], math=m, fusion=%(default)d))
+"""
+
+# the module-level lists of tests/test_gpu_pointwise_paths.py: the same calls on host tensors, no reference computed
+POINTWISE_REPLAY = ENGINE + r"""
+import test_gpu_pointwise_paths as TQ
+def run(lst, name, f):
+    say("fg-job " + json.dumps(dict(list=lst, kind="pointwise", case=name, shape=[], math=0, fusion=%(default)d)))
+    say("fg-pass run")
+    f()
+    say("fg-rc 0")
+for c in TQ.CAP_CASES: run("CAP_CASES", c[0], lambda: TQ.run_cap(ctx, c, dry=True))
+for c in TQ.BN_CASES + [TQ.OFFSET_CASE]: run("BN_CASES", "%%dx%%d" %% c, lambda: TQ.run_bn(ctx, c, dry=True))
+for c in TQ.OPT_CASES: run("OPT_CASES", c[0], lambda: TQ.run_opt(ctx, c, dry=True))
+for c in TQ.RNG_CASES: run("RNG_CASES", "seed%%x-off%%x-n%%d" %% c, lambda: TQ.run_rng(ctx, c, dry=True))
+# the remaining single-process entries, called as their GPU tests call them (tests/test_gpu_sampler.py, test_gpu_memory_contract.py
+# test_parzen_min_dist, test_gpu_bench.py): which kernels stand behind fg_rank_scores, fg_image_grid, fg_parzen_min_dist, fg_prof_clock_start
+def other_entries():
+    E, P = torch.empty, (lambda t: t.data_ptr())
+    n = 37
+    order, nb = torch.empty(n, dtype=torch.int32), lib.fg_rank_scores_workspace_bytes(37)
+    scr = E(nb // 4 + 1)
+    ctx.check(lib.fg_rank_scores(ctx.h, P(E(n)), n, 0, P(order), P(scr), nb))
+    grid, mm = E(3 * 64 * 64), E(2)
+    ctx.check(lib.fg_image_grid(ctx.h, P(E(n, 8, 8, 3)), P(order), 6, 3, 8, 8, 3, 2, 1, P(grid), P(mm)))
+    ctx.check(lib.fg_parzen_min_dist(ctx.h, P(E(5, 300)), P(E(300)), P(E(300)), 5, 300, P(E(5)), P(E(1))))
+    ctx.check(lib.fg_prof_clock_start(ctx.h, 1.0))
+run("OTHER_ENTRIES", "rank-grid-parzen-clock", other_entries)
 """
 
 REPLAY = ENGINE + r"""
@@ -225,10 +294,10 @@ def parse_jobs(lines):
     jobs, cur, p = [], None, None
     for l in lines:
         if l.startswith("fg-job "):
-            cur = json.loads(l[7:]); cur["rc"] = {}; cur["sigs"] = {}
+            cur = json.loads(l[7:]); cur["rc"] = {}; cur["sigs"] = {}; cur["grids"] = {}
             jobs.append(cur)
         elif l.startswith("fg-pass "):
-            p = l[8:]; cur["sigs"][p] = []
+            p = l[8:]; cur["sigs"][p] = []; cur["grids"][p] = []
         elif l.startswith("fg-rc "):
             parts = l[6:].split(" ", 1)
             cur["rc"][p] = (int(parts[0]), parts[1] if len(parts) > 1 else "")
@@ -237,6 +306,7 @@ def parse_jobs(lines):
             s = sig_of(l)
             assert s, l
             cur["sigs"][p].append(s)
+            cur["grids"][p].append((kernel_of(s[0]),) + tuple(int(v) for v in LAUNCH_RE.match(l).group(2, 3, 4)))
     return jobs
 
 
@@ -250,6 +320,9 @@ def replay():
 
 
 def flops(job, p=None):
+    if job["kind"] == "sconv":
+        B, H, W, Cin, Cout, k = job["shape"]
+        return 2.0 * B * (H // 2) * (W // 2) * k * k * Cin * Cout
     if job["kind"] == "lin":
         B, K, N = job["shape"]
         return 2.0 * B * K * N
@@ -310,6 +383,50 @@ def sweep():
         os.unlink(f.name)
 
 
+STRIDED_SEED, STRIDED_N = 20261019, 200
+STRIDED_PASSES = ("create", "fwd", "bwd")
+
+
+def strided_geometries():
+    """(B, H, W, cin, cout, k): k in {3, 5, 7}, even H, W in 2..32, channels from CHANNELS, B in 1..64"""
+    import numpy as np
+    rng = np.random.default_rng(STRIDED_SEED)
+    out = []
+    for i in range(STRIDED_N):
+        k = int(rng.choice([3, 5, 7]))
+        h, w = 2 * int(rng.integers(1, 17)), 2 * int(rng.integers(1, 17))
+        cin, cout = int(rng.choice(CHANNELS)), int(rng.choice(CHANNELS))
+        out.append((int(round(2 ** rng.uniform(0, 6))), h, w, cin, cout, k))
+    return out
+
+
+def _run_jobs(code, jobs):
+    import tempfile
+    with tempfile.NamedTemporaryFile("w", suffix=".json", delete=False) as f:
+        json.dump(jobs, f)
+    try:
+        return parse_jobs(_run(code, [f.name]))
+    finally:
+        os.unlink(f.name)
+
+
+def strided_sweep(extra=()):
+    """every strided geometry (+ extra ones) in math 0 / 6 with the fusion default and the Winograd bits cleared, as one-layer nets"""
+    jobs = [dict(list="strided-sweep", kind="sconv", shape=list(s), math=m, fusion=fl)
+            for s in list(strided_geometries()) + list(extra) for m in (0, 6) for fl in (FG_FUSE_DEFAULT, FG_FUSE_DEFAULT & ~WINO_ALL)]
+    return _run_jobs(STRIDED, jobs)
+
+
+def pointwise_replay():
+    """CAP_CASES, BN_CASES, OPT_CASES and RNG_CASES of tests/test_gpu_pointwise_paths.py -> parsed jobs (one pass, "run")"""
+    return parse_jobs(_run(POINTWISE_REPLAY))
+
+
+def strided_replay():
+    """STRIDED_CASES of tests/test_gpu_strided_conv.py under that module's settings"""
+    return parse_jobs(_run(STRIDED_REPLAY))
+
+
 def net_launches():
     """{tag: [launch line, ...]} of the second (steady-state) iteration of each baseline pair, plus the set of all kernel texts"""
     return _split_nets(_run(NETS), "1")
@@ -346,12 +463,200 @@ def launch_sites():
     return sites
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# capped-grid census: a launch whose grid is capped below its work count needs a kernel that walks the rest
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _strip_comments(t):
+    t = re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group(0)), t, flags=re.S)
+    return re.sub(r"//[^\n]*", "", t)
+
+
+def _matching(t, i, op="(", cl=")"):
+    """index just behind the bracket that closes the one at t[i]"""
+    d = 0
+    for j in range(i, len(t)):
+        if t[j] == op:
+            d += 1
+        elif t[j] == cl:
+            d -= 1
+            if d == 0:
+                return j + 1
+    raise ValueError("unbalanced %s at %d" % (op, i))
+
+
+def _split_args(t):
+    out, d, cur = [], 0, ""
+    for ch in t:
+        if ch in "([{":
+            d += 1
+        elif ch in ")]}":
+            d -= 1
+        if ch == "," and d == 0:
+            out.append(cur.strip()); cur = ""
+        else:
+            cur += ch
+    out.append(cur.strip())
+    return out
+
+
+_NUM = r"(\d+|[A-Z][A-Z0-9_]{2,})"
+# `e < N ? e : N`, `min(e, N)` / `std::min`, `if (v > N) v = N`
+_CAPS = [re.compile(r"<\s*" + _NUM + r"\s*\?[^:;]*:\s*\1\b"), re.compile(r"\bmin\s*(?:<[^>]*>)?\s*\([^;]*,\s*" + _NUM + r"\s*\)"),
+         re.compile(r"\bmin\s*(?:<[^>]*>)?\s*\(\s*(?:\([\w ]+\)\s*)?" + _NUM + r"\s*,"), re.compile(r"if\s*\(\s*[\w.]+\s*>\s*" + _NUM + r"\s*\)\s*[\w.]+\s*=\s*\1\s*;")]
+
+
+def _cap_in(expr, helpers):
+    """-> the cap an expression carries (text of N), or None"""
+    for r in _CAPS:                     # an explicit cap first: `if (grid.x > 1024) ..` behind an FG_GRID( is the tighter one
+        m = r.search(expr)
+        if m:
+            return m.group(1)
+    for name, n in helpers.items():
+        if re.search(r"\b%s\s*\(" % re.escape(name), expr):
+            return n
+    return None
+
+
+def capped_launches():
+    """-> [dict(kernel, site, cap, dim, strides)] for every hipLaunchKernelGGL( in csrc/*.hip whose grid expression is capped in
+    some dimension: through FG_GRID( or another helper whose own definition holds a cap, an explicit min(.., N) / `< N ? .. : N`, or
+    a following `if (grid.x > N) grid.x = N`.  `strides` says whether the kernel's body, or a __device__ function it names, reads
+    gridDim in that dimension -- a grid-stride loop, or a partition of the work by the number of blocks."""
+    texts = {fn: _strip_comments(open(os.path.join(CSRC, fn)).read()) for fn in sorted(os.listdir(CSRC)) if fn.endswith((".hip", ".h"))}
+    # helpers: macros and small functions whose definition carries a cap
+    helpers = {}
+    for fn, t in texts.items():
+        for m in re.finditer(r"#define\s+(\w+)\(([^)]*)\)((?:[^\n\\]|\\\n)*)", t):
+            c = _cap_in(m.group(3), {})
+            if c:
+                helpers[m.group(1)] = c
+        for m in re.finditer(r"\bstatic\s+inline\s+(?:int|long long|unsigned)\s+(\w+)\s*\([^)]*\)\s*\{", t):
+            body = t[m.end() - 1:_matching(t, m.end() - 1, "{", "}")]
+            c = _cap_in(body, {})
+            if c:
+                helpers[m.group(1)] = c
+    # bodies of kernels and __device__ functions
+    bodies, kernels = {}, set()
+    for fn, t in texts.items():
+        for m in re.finditer(r"__(global|device)__\s*(?:__launch_bounds__\s*\([^)]*\)\s*)?[^;{}()]*?\b(\w+)\s*\(", t):
+            e = _matching(t, m.end() - 1)
+            k = re.match(r"\s*(?:const\s*)?\{", t[e:])
+            if not k:
+                continue
+            b0 = e + k.end() - 1
+            bodies[m.group(2)] = bodies.get(m.group(2), "") + t[b0:_matching(t, b0, "{", "}")]
+            if m.group(1) == "global":
+                kernels.add(m.group(2))
+
+    def closure(name):
+        seen, todo, out = set(), [name], ""
+        while todo:
+            n = todo.pop()
+            if n in seen or n not in bodies:
+                continue
+            seen.add(n)
+            out += bodies[n]
+            todo += [w for w in set(re.findall(r"\b[A-Za-z_]\w*\b", bodies[n])) if w in bodies and w not in kernels]
+        return out
+
+    macros = {m.group(1): int(m.group(2)) for t in texts.values() for m in re.finditer(r"#define\s+([A-Z][A-Z0-9_]+)\s+(\d+)\s*$", t, flags=re.M)}
+    for t in texts.values():            # one macro named after another (TW_BLOCKS)
+        for m in re.finditer(r"#define\s+([A-Z][A-Z0-9_]+)\s+([A-Z][A-Z0-9_]+)\s*$", t, flags=re.M):
+            if m.group(2) in macros:
+                macros[m.group(1)] = macros[m.group(2)]
+    out = []
+    for fn, t in texts.items():
+        if not fn.endswith(".hip"):
+            continue
+        for m in re.finditer(r"hipLaunchKernelGGL\s*\(", t):
+            if t[max(0, m.start() - 8):m.start()].endswith("#define "):
+                continue
+            args = _split_args(t[m.end():_matching(t, m.end() - 1) - 1])
+            kernel, grid = kernel_of(args[0]), args[1]
+            line = t.count("\n", 0, m.start()) + 1
+            # the enclosing function's text in front of the launch: definitions of the names the grid expression uses
+            start = max(t.rfind("\n}\n", 0, m.start()), 0)
+            before = t[start:m.start()]
+
+            def resolve(expr, depth=0):
+                comps = [expr]
+                mm = re.match(r"^(?:dim3\s*)?\((.*)\)$", expr, flags=re.S) if expr.startswith(("dim3", "(")) else None
+                if mm and _matching(expr, expr.index("(")) == len(expr):
+                    comps = _split_args(mm.group(1))
+                res = []
+                for c in comps:
+                    extra = ""
+                    if depth < 3:
+                        for ident in set(re.findall(r"\b[a-z_]\w*\b", c)):
+                            # (the definition and the clamp nearest to the launch)
+                            for d in list(re.finditer(r"\b(?:dim3|int|long long|unsigned|auto)\s+%s\s*(?:=\s*([^;]*);|\(([^;]*)\)\s*;)" % re.escape(ident), before))[-1:]:
+                                sub = d.group(1) if d.group(1) is not None else "dim3(" + d.group(2) + ")"
+                                if re.fullmatch(r"\w+", c) and (sub.startswith("dim3") or d.group(2) is not None):
+                                    return resolve(sub, depth + 1) if not res else res + resolve(sub, depth + 1)
+                                extra += " " + " ".join(resolve(sub, depth + 1))
+                            for d in list(re.finditer(r"if\s*\(\s*%s(?:\.x)?\s*>\s*%s\s*\)\s*%s(?:\.x)?\s*=\s*\1\s*;" % (re.escape(ident), _NUM, re.escape(ident)), before))[-1:]:
+                                extra += " " + d.group(0)
+                    res.append(c + extra)
+                return res
+            comps = resolve(grid)
+            # `if (grid.x > N) grid.x = N` behind a dim3 variable
+            if re.fullmatch(r"\w+", grid):
+                for d in re.finditer(r"if\s*\(\s*%s\.([xy])\s*>\s*%s\s*\)\s*%s\.\1\s*=\s*\2\s*;" % (grid, _NUM, grid), before):
+                    i = "xy".index(d.group(1))
+                    while len(comps) <= i:
+                        comps.append("")
+                    comps[i] = d.group(0) + " " + comps[i]
+            for dim, c in zip("xyz", comps):
+                cap = _cap_in(c, helpers)
+                if cap is None:
+                    continue
+                body = closure(kernel)
+                assert body, "no body found for kernel %s (%s:%d)" % (kernel, fn, line)
+                out.append(dict(kernel=kernel, site="%s:%d" % (fn, line), cap=int(cap) if cap.isdigit() else macros[cap], dim=dim, strides=bool(re.search(r"\bgridDim\.%s\b" % dim, body))))
+    return out
+
+
+def at_cap(jobs, kernel, dim, cap):
+    """the jobs (parsed logs) with a launch of `kernel` whose grid has `cap` blocks in `dim` (bn_apply_blocks rounds the clamped
+    count up to its unit: or a few more): the launcher clamped it"""
+    i = 1 + "xyz".index(dim)
+    return [j for j in jobs if any(g[0] == kernel and g[i] >= cap for v in j["grids"].values() for g in v)]
+
+
+def job_id(j):
+    return (j["list"], j.get("case") or "x".join(str(v) for v in j["shape"]) + ("-math%d" % j["math"] if j.get("math") else ""))
+
+
+def all_logs(replay_jobs, strided_jobs, pointwise_jobs, nets):
+    """every parsed log as one job list; a net iteration becomes the job ("net", tag)"""
+    jobs = list(pointwise_jobs) + list(strided_jobs) + list(replay_jobs)
+    for tag, lines in nets.items():
+        g = [(kernel_of(sig_of(l)[0]),) + tuple(int(v) for v in LAUNCH_RE.match(l).group(2, 3, 4)) for l in lines]
+        jobs.append(dict(list="net", case=tag, shape=[], grids=dict(run=g), sigs=dict(run=[sig_of(l) for l in lines]), rc={}))
+    return jobs
+
+
+def capped_rows(path=LEDGER):
+    """the "Capped launchers" table of DISPATCH_COVERAGE.md: {(kernel, dim): (cap, unit of work, covering case)}"""
+    rows, inside = {}, False
+    for l in open(path):
+        if l.startswith("## "):
+            inside = l.startswith("## Capped launchers")
+        m = re.match(r"^\| `(\w+)` \| ([xyz]) \| (\S+) \| (.*?) \| (.*) \|\s*$", l)
+        if inside and m:
+            assert (m.group(1), m.group(2)) not in rows
+            rows[(m.group(1), m.group(2))] = (m.group(3), m.group(4).strip(), m.group(5).strip())
+    return rows
+
+
 def ledger_rows(path=LEDGER):
     """the ledger table of DISPATCH_COVERAGE.md: {kernel name: (status, note)}; a duplicated name is an error"""
-    rows = {}
+    rows, inside = {}, False
     for l in open(path):
+        if l.startswith("## "):
+            inside = l.startswith("## Ledger")
         m = re.match(r"^\| `(\w+)` \| (\S+) \| (.*) \|\s*$", l)
-        if m:
+        if m and inside:
             assert m.group(1) not in rows, "ledger lists %s twice" % m.group(1)
             rows[m.group(1)] = (m.group(2), m.group(3).strip())
     return rows

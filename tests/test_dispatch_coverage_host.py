@@ -16,6 +16,14 @@ LDS_PLAIN = 64 * 1024           # dynamic LDS a launch may ask for without hipFu
 # configurations: their signature is (launch site, block) alone -- DISPATCH_COVERAGE.md, "Known limits".
 SHAPE_SIZED_LDS = {"thin_out_slab_mfma_kernel", "gemv_bwd_kernel"}
 STATUSES = {"operator", "net-only", "measure-only", "unreachable", "other-entry"}
+# `other-entry` is for kernels that no single planning-only process can launch: the sync-BN exchange needs the pause / all-reduce
+# protocol of a second rank, the clock probe a device clock (fg_prof_clock_start launches nothing in a planning-only context)
+OTHER_ENTRY = {"bn_sync_local_kernel", "bn_sync_global_kernel", "bn_bwd_sync_local_kernel", "bn_bwd_sync_global_kernel", "clock_probe_kernel"}
+
+
+# capped launchers that STRIDED_CASES launch as part of a contraction plan, below their caps (their work count follows from the
+# plan: split-K partials of a ragged layer, padded copies of thin operands)
+CONTRACTION_SIDE = {"sum_splits_scalar_kernel", "thin_pad_kernel"}
 
 
 def norm(sig):
@@ -31,9 +39,14 @@ def audit():
     from face_generator_amd import build
     build.build(verbose=False)
     t0 = time.time()
-    out = dict(replay=A.replay(), sweep=A.sweep(), nets=A.net_launches())
+    out = dict(replay=A.replay(), sweep=A.sweep(), nets=A.net_launches(),
+               strided_replay=A.strided_replay(), strided_sweep=A.strided_sweep(extra=STRIDED_REFUSED), pointwise=A.pointwise_replay())
     out["seconds"] = time.time() - t0
     return out
+
+
+# stride-2 layers that include/facegen_hip.h rules out (odd H, odd W, k = 9), appended to the strided sweep: fg_net_create must refuse them
+STRIDED_REFUSED = [(2, 5, 8, 8, 16, 3), (2, 8, 7, 6, 10, 5), (1, 8, 8, 8, 8, 9)]
 
 
 def thin_layer(cs, cw, k):
@@ -65,6 +78,59 @@ def test_every_reachable_signature_is_covered_by_an_operator_level_case(audit):
     best = A.smallest_per_signature(audit["sweep"])
     missing = sorted((s for s in A.all_sigs(audit["sweep"]) if norm(s) not in covered), key=str)
     assert not missing, "reachable but never compared with a reference:\n" + "\n".join("%s  smallest: %s" % (s, best.get(s)) for s in missing)
+
+
+def test_the_strided_sweep_is_the_one_the_ledger_describes(audit):
+    geo = A.strided_geometries()
+    assert len(geo) == A.STRIDED_N == 200
+    assert {g[5] for g in geo} == {3, 5, 7} and all(g[1] % 2 == 0 and g[2] % 2 == 0 and 2 <= g[1] <= 32 and 2 <= g[2] <= 32 for g in geo)
+    assert {g[3] for g in geo} | {g[4] for g in geo} == set(A.CHANNELS) and min(g[0] for g in geo) == 1 and 32 < max(g[0] for g in geo) <= 64
+    assert any(g[4] % 4 for g in geo) and any(g[3] % 4 for g in geo)
+    jobs = audit["strided_sweep"]
+    assert len(jobs) == 4 * (len(geo) + len(STRIDED_REFUSED))
+    assert {(j["math"], j["fusion"]) for j in jobs} == {(0, 503), (6, 503), (0, 503 & ~A.WINO_ALL), (6, 503 & ~A.WINO_ALL)}
+    text = open(A.LEDGER).read()
+    assert "seed %d" % A.STRIDED_SEED in text and "%d strided geometries" % len(geo) in text
+
+
+def test_every_signature_of_the_strided_sweep_is_run_by_a_strided_case(audit):
+    """(a) for stride 2: whatever a one-layer net [FG_CONV p=2] launches in forward and backward at any swept geometry, some case of
+    tests/test_gpu_strided_conv.py launches too, under the settings that module runs it with"""
+    import test_gpu_strided_conv as TS
+    rep = audit["strided_replay"]
+    assert [tuple(j["shape"]) for j in rep if j["math"] == 0] == list(TS.STRIDED_CASES)
+    assert [(tuple(j["shape"]), j["math"]) for j in rep if tuple(j["shape"]) != TS.CAP_CASE] == TS.RUNS
+    assert all(j["rc"][p] == (0, "") for j in rep for p in A.STRIDED_PASSES), [(j["shape"], j["rc"]) for j in rep if any(v[0] for v in j["rc"].values())]
+    covered = {norm(s) for s in A.all_sigs(rep)}
+    best = A.smallest_per_signature(audit["strided_sweep"])
+    missing = sorted((s for s in A.all_sigs(audit["strided_sweep"]) if norm(s) not in covered), key=str)
+    assert not missing, "reachable at stride 2 but never compared with a reference:\n" + "\n".join("%s  smallest: %s" % (s, best.get(s)) for s in missing)
+    # what the cases are there for: both zero-insert kernels, the capped one above its cap
+    cap = [j for j in rep if tuple(j["shape"]) == TS.CAP_CASE][0]
+    B, H, W, cin, cout, k = TS.CAP_CASE
+    assert ("zero_insert2_kernel", 256, 0) in cap["sigs"]["bwd"] and B * H * W * cout // 4 > 4096 * 256
+    assert any(("zero_insert2_scalar_kernel", 256, 0) in j["sigs"]["bwd"] for j in rep if j["shape"][4] % 4)
+
+
+def test_a_strided_layer_is_refused_at_create_time_or_runs_every_pass(audit):
+    """(b) for stride 2: a layer that fg_net_create accepts returns FG_OK from the forward pass and from the backward pass with
+    FG_BWD_PARAM_GRADS | FG_BWD_INPUT_GRAD, in a workspace of exactly fg_net_workspace_bytes; a refused one is refused by
+    fg_net_create with FG_ERR_UNSUPPORTED naming the layer, and exactly the layers the header rules out are refused (before the
+    scalar zero insert, Cout % 4 != 0 was created, ran forward and failed in backward: "zero_insert2: C % 4")"""
+    bad, refused = [], set()
+    for j in audit["strided_sweep"]:
+        B, H, W, cin, cout, k = j["shape"]
+        stated = bool(H % 2 or W % 2 or k > 7)
+        rc = j["rc"]
+        if stated:
+            refused.add(tuple(j["shape"]))
+            ok = rc["create"][0] == -4 and "layer 0" in rc["create"][1] and set(rc) == {"create"} and not any(j["sigs"].values())
+        else:
+            ok = all(rc.get(p) == (0, "") for p in A.STRIDED_PASSES)
+        if not ok:
+            bad.append((j["shape"], j["math"], j["fusion"], rc))
+    assert not bad, "%d jobs; first: %s" % (len(bad), bad[:5])
+    assert refused == set(STRIDED_REFUSED)
 
 
 def test_the_new_cases_take_the_signatures_written_next_to_them(audit):
@@ -203,8 +269,9 @@ def test_every_launch_site_is_entered_in_the_ledger_with_one_status(audit):
     rows = A.ledger_rows()
     assert sorted(rows) == sorted(sites), "ledger and csrc/*.hip disagree: %s" % sorted(set(rows) ^ set(sites))
     assert all(st in STATUSES for st, _ in rows.values()), {k: v for k, v in rows.items() if v[0] not in STATUSES}
-    repk = {A.kernel_of(s[0]) for s in A.all_sigs(audit["replay"])}
-    swk = {A.kernel_of(s[0]) for s in A.all_sigs(audit["sweep"])}
+    # replay: the conv / linear lists, STRIDED_CASES, and the module-level lists of tests/test_gpu_pointwise_paths.py
+    repk = {A.kernel_of(s[0]) for k in ("replay", "strided_replay", "pointwise") for s in A.all_sigs(audit[k])}
+    swk = {A.kernel_of(s[0]) for k in ("sweep", "strided_sweep") for s in A.all_sigs(audit[k])}
     netk = {A.kernel_of(A.sig_of(l)[0]) for v in audit["nets"].values() for l in v}
     meas = measure_only_sites()
     tests = set(os.listdir(os.path.join(A.ROOT, "tests")))
@@ -219,7 +286,58 @@ def test_every_launch_site_is_entered_in_the_ledger_with_one_status(audit):
         elif st == "unreachable":
             assert k not in repk | swk | netk and k not in meas, "%s is reached" % k
             assert len(note) > 20, "%s: say which earlier branch shadows it" % k
-        else:       # other-entry: launched by entries outside the conv / linear contraction family
+        else:       # other-entry: the explicit allow-list above, nothing else
+            assert k in OTHER_ENTRY, "%s: other-entry is for %s only; replay its entry in tests/dispatch_audit.py" % (k, sorted(OTHER_ENTRY))
             assert k not in repk | swk | netk and k not in meas, k
             assert any(t in tests for t in re.findall(r"test_gpu_\w+\.py", note)), "%s: name the GPU test of its entry" % k
     assert meas <= {k for k, v in rows.items() if v[0] == "measure-only"}
+    assert OTHER_ENTRY == {k for k, v in rows.items() if v[0] == "other-entry"}
+    # the two rows that were false: the scalar BatchNorm reductions are launched by BN_CASES with C = 12 / 96 / 2048, by nothing before
+    bn = {j["case"]: {A.kernel_of(s[0]) for s in j["sigs"]["run"]} for j in audit["pointwise"] if j["list"] == "BN_CASES"}
+    for case in ("3x12", "16421x96", "70x2048", "349600x12"):
+        assert {"bn_stats_partial_kernel", "bn_bwd_partial_kernel"} <= bn[case] and not {"bn_stats4_partial_kernel", "bn_bwd4_partial_kernel"} & bn[case], case
+    for case in ("5000x4", "130x1024", "2x8", "16421x8", "4096x64"):
+        assert {"bn_stats4_partial_kernel", "bn_bwd4_partial_kernel"} <= bn[case], case
+    assert not {"bn_stats_partial_kernel", "bn_bwd_partial_kernel"} & {A.kernel_of(s[0]) for s in A.all_sigs(audit["replay"])}
+
+
+def test_no_capped_grid_without_a_loop():
+    """Every launch whose grid expression is capped (FG_GRID(, cr_rowblocks(, bn_apply_blocks(, an explicit min(.., N) or
+    `< N ? .. : N`, a following `if (grid.x > N) grid.x = N`, the `rows < 32768` of launch_rows) names a kernel whose body, or a
+    __device__ function it calls, reads gridDim in the capped dimension: a grid-stride loop, or a division of the work by the number
+    of blocks.  A kernel that handles one unit per thread and returns drops everything above the cap, silently."""
+    caps = A.capped_launches()
+    names = {c["kernel"] for c in caps}
+    assert len(caps) >= 70 and {"zero_insert2_kernel", "zero_insert2_scalar_kernel", "adam_kernel", "rng_kernel", "bn_apply_kernel", "bn_stats_partial_kernel",
+                                "sum_splits_kernel", "split_planes_kernel", "thin_in_mfma_pad_kernel", "thin_out_kernel", "thin_out_win_kernel",
+                                "thin_wgrad_mfma_kernel"} <= names
+    cap = {(c["kernel"], c["dim"]): c["cap"] for c in caps}
+    assert cap["prelu_bwd_kernel", "x"] == cap["actpool_bwd_kernel", "x"] == cap["maxpool_prelu_bwd_kernel", "x"] == 1024
+    assert cap["norms_partial_kernel", "x"] == 512 and cap["rows_join_split_kernel", "y"] == 32768 and cap["fill_kernel", "x"] == 4096
+    assert cap["bn_stats4_partial_kernel", "x"] == 256 and cap["thin_in_mfma_pad_kernel", "x"] == 1024 and cap["thin_in_mfma_kernel", "x"] == 2048
+    bad = ["%s (%s): gridDim.%s capped at %d" % (c["kernel"], c["site"], c["dim"], c["cap"]) for c in caps if not c["strides"]]
+    assert not bad, "launched with a capped grid by a kernel that never reads gridDim in that dimension:\n" + "\n".join(bad)
+
+
+def test_the_capped_launchers_table_is_the_census_and_its_cases_reach_the_cap(audit):
+    """tests/DISPATCH_COVERAGE.md, "Capped launchers": one row per (kernel, dimension) of the census with its cap; the case named in
+    the last column launches the kernel with the clamped grid (planning-only log), and "none" is true: no list and no net
+    iteration does.  Every capped launcher that the module-level lists of tests/test_gpu_pointwise_paths.py or STRIDED_CASES reach
+    has such a case."""
+    census = {(c["kernel"], c["dim"]): c["cap"] for c in A.capped_launches()}
+    rows = A.capped_rows()
+    assert sorted(rows) == sorted(census), set(rows) ^ set(census)
+    jobs = A.all_logs(audit["replay"], audit["strided_replay"], audit["pointwise"], audit["nets"])
+    by_id = {A.job_id(j): j for j in jobs}
+    module_level = {A.kernel_of(s[0]) for k in ("strided_replay", "pointwise") for s in A.all_sigs(audit[k])}
+    for (k, d), (cap, unit, cover) in sorted(rows.items()):
+        assert int(cap) == census[k, d] and unit, (k, d, cap)
+        hits = A.at_cap(jobs, k, d, census[k, d])
+        m = re.match(r"`([^`]+)` `([^`]+)`", cover)
+        if m:
+            assert (m.group(1), m.group(2)) in by_id, "%s: no job %s" % (k, m.groups())
+            assert by_id[m.group(1), m.group(2)] in hits, "%s: %s %s does not launch it with %d blocks in %s" % ((k,) + m.groups() + (census[k, d], d))
+            # above the cap, not at it: the pointwise and strided cases are sized 259 units (x 4) past 4096 x 256 and asserted there
+        else:
+            assert cover.startswith("none") and not hits, "%s: %s" % (k, [A.job_id(j) for j in hits][:3])
+            assert k not in module_level or k in CONTRACTION_SIDE, "%s is reached by a module-level list: give it a case above its cap" % k
