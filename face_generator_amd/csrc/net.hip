@@ -87,6 +87,7 @@ struct fg_net {
     const float* const* masks = nullptr;
     std::vector<const float*> mask_ptrs;
     int last_train = 1;
+    bool fwd_done = false;            // the last forward call ran to its end: the workspace holds what `plan_batch` / `last_train` describe
     // ranged backward state (fg_net_backward_range)
     const float* bwd_gcur = nullptr;
     int bwd_pp = 0, bwd_next = -1;
@@ -535,6 +536,7 @@ static int forward_run(fg_net* n, long long* out_offset) {
         cur = y;
     }
     n->run_phase = 0;
+    n->fwd_done = true;
     if (out_offset) *out_offset = n->st.back().out_off;
     return FG_OK;
 }
@@ -1032,6 +1034,9 @@ int fg_net_forward(fg_net* n, int B, const float* x, void* wsv, size_t ws_bytes,
 int fg_net_forward_to(fg_net* n, int B, const float* x, void* wsv, size_t ws_bytes, int train, const float* const* masks,
                       int n_masks, long long* out_offset, float* out_override) {
     if (!n || !x || !wsv) return fg_set_err(n ? n->ctx : nullptr, FG_ERR_INVALID, "fg_net_forward: null argument");
+    // a forward that is refused, fails or stays paused leaves nothing a backward pass may run over (make_plan below already describes
+    // the NEW batch), and whatever an earlier ranged or paused pass has left is void (no _resume over this call's plan) until one ends
+    n->fwd_done = false; n->bwd_next = -1; n->run_phase = 0;
     if (out_override && ((uintptr_t)out_override & 15)) return fg_set_err(n->ctx, FG_ERR_INVALID, "fg_net_forward_to: 16-byte alignment");
     n->out_override = out_override;
     fg_ctx* ctx = n->ctx;
@@ -1092,6 +1097,7 @@ int fg_net_backward_range(fg_net* n, int B, const float* x, const float* gy, voi
     fg_ctx* ctx = n->ctx;
     const int last = (int)n->st.size() - 1;
     if (stage_from > last || stage_to < 0 || stage_from < stage_to) return fg_set_err(ctx, FG_ERR_INVALID, "fg_net_backward_range: bad range");
+    if (!n->fwd_done) return fg_set_err(ctx, FG_ERR_INVALID, "fg_net_backward: the last forward was refused or has not finished");
     if (n->plan_batch != B) return fg_set_err(ctx, FG_ERR_INVALID, "fg_net_backward: batch %d != forward batch %d", B, n->plan_batch);
     if (!n->last_train) return fg_set_err(ctx, FG_ERR_INVALID, "fg_net_backward: last forward was in evaluate mode");
     if ((size_t)n->total_floats * sizeof(float) > ws_bytes) return fg_set_err(ctx, FG_ERR_WORKSPACE, "fg_net_backward: workspace");

@@ -631,6 +631,7 @@ int fg_step_D(fg_gan* g, int B, const float* real, const float* cond_real, const
     g->d_out_off = off; g->last_B[0] = B;
     int* conf = (int*)(g->ws + g->o_conf);
     if ((rc = fg_launch_bce(ctx, g->wsD + off, g->ws + g->o_targets, g->ws + g->o_loss, g->ws + g->o_dprob, conf, B))) return rc;
+    g->grads_local[0] = 0;      // the backward below overwrites what an earlier FG_STEP_NO_UPDATE step held for fg_gan_update
     rc = fg_net_backward(g->D, B, din, g->ws + g->o_dprob, g->wsD, g->wsD_bytes, FG_BWD_PARAM_GRADS, nullptr);
     if ((rc = gan_drain(g, g->D, rc, false))) return rc;
     if (flags & FG_STEP_NO_UPDATE) {
@@ -679,6 +680,7 @@ int fg_step_G(fg_gan* g, int B, const float* cond, const float* noise, const flo
     float* gG = nullptr;
     fg_net_vectors(g->G, nullptr, &gG, nullptr);
     const bool update = !(flags & FG_STEP_NO_UPDATE);
+    g->grads_local[1] = 0;      // G's gradients are overwritten from here on: a held FG_STEP_NO_UPDATE gradient is gone
     if (update && gan_exchange(g) && g->overlap) {
         // bucketed all-reduce overlapped with backward: G's gradients are produced output -> input; each finished ~1 M-parameter
         // range of the flat vector goes onto the communicator's stream while the earlier layers still compute

@@ -189,6 +189,25 @@ typedef struct fg_layer_spec {
     float p, q;
 } fg_layer_spec;
 
+/* CALL ORDER (fg_net_*).  A net carries state from call to call -- the plan of the last forward, packed copies of its weights, what
+ * a paused or ranged pass has left -- and none of it may show in a result: whatever ran before, a call gives the bits a freshly created
+ * net bound to the same vectors gives (tests/CALL_ORDER.md lists every field and the scenario that would see it stale).
+ *   Legal, at any batch up to the one the workspace was sized for and in any order: forwards at changing batches and in changing
+ *   modes (train / evaluate); a forward without a backward; fg_net_backward any number of times after ONE train forward (the gradient
+ *   vector is overwritten, never accumulated, so the second call leaves the bits of the first); FG_BWD_PARAM_GRADS and
+ *   FG_BWD_INPUT_GRAD in two calls instead of one; fg_net_backward_range over any descending split of the stages; a NEW forward at any
+ *   time -- it abandons a paused pass (FG_PAUSED_SYNC not resumed) and an unfinished range, also when it is itself refused: neither
+ *   _resume entry continues over the plan of a forward that never ran; fg_net_forward after fg_net_forward_to
+ *   (the output is in the workspace again); fg_set_math and fg_set_fusion between any two calls, also between a forward and its
+ *   backward (a PReLU backward that leaves or joins its neighbour's epilogue that way sums its slope gradient in another order; a
+ *   net created with FG_FUSE_WFINISH_BATCH cleared keeps reducing per layer when the bit is set later); fg_net_bind to other vectors,
+ *   and any write to the parameter vector that is followed by fg_net_params_changed.
+ *   Refused with FG_ERR_INVALID, nothing launched: fg_net_backward / fg_net_backward_range unless the LAST forward call was a train
+ *   forward at that batch that ran to its end -- not after an evaluate forward, and not after a forward that was itself refused
+ *   (FG_ERR_WORKSPACE, a bad batch, missing masks ...), failed or is still paused: the workspace then does not hold that batch's
+ *   activations; fg_net_backward_range that does not start at the last stage or continue exactly where the previous call of the SAME
+ *   forward stopped; fg_net_forward_resume / fg_net_backward_resume when that pass is not paused; fg_net_layer_output of the last
+ *   layer while fg_net_forward_to has redirected it. */
 int fg_net_create(fg_ctx* ctx, const fg_layer_spec* layers, int n_layers, int in_c, int in_h, int in_w, fg_net** out);
 int fg_net_destroy(fg_net* net);
 long long fg_net_num_params(const fg_net* net);   /* length of the flat parameter vector (reference order) */
@@ -322,6 +341,22 @@ int fg_comm_schedule(fg_comm* comm, char* buf, size_t len, int reset);
  *      until D is next evaluated or fg_gan_finish_pending), G's is bucketed under its own backward; sync_bn = exact
  *      global-batch BatchNorm statistics (fp64 sums reduced at every BatchNorm).  overlap: 0 = blocking exchange, 1 =
  *      overlapped, 2 = overlapped even on a one-rank communicator (exercises the N > 1 path on one GPU). ---- */
+/* CALL ORDER (fg_gan_*).  Steps may follow each other in any order and at any even batch from 2 to max_batch (an epoch's short last
+ * batch), and the nets may be used between them by anything that leaves their vectors alone -- an fg_sampler on the same nets and
+ * workspaces, fg_net_forward in either mode: the next step gives the bits it would have given without the visit.
+ *   A FG_STEP_NO_UPDATE step holds its gradients for fg_gan_update until the next step of the SAME kind overwrites them; a step of the
+ *   other kind in between does not disturb them (a G-step forms no gradients of D).  fg_gan_update with nothing held -- never stepped,
+ *   already applied, or overwritten by a later step -- is refused (FG_ERR_INVALID).  The step count moves only when an update is
+ *   applied.  FG_GAN_CONFUSION int[4..7] (the global batch) is written by FG_STEP_NO_UPDATE D-steps only: it is the gate's input and
+ *   keeps the counts of the last gated step through plain ones.
+ *   Library-drawn noise and masks: every draw of `count` floats advances its offset by ceil(count / 4), the noise of a closure being
+ *   fg_rng_uniform(noise_seed, noise_offset, count, -1, 1); explicit noise / masks leave the offsets alone.
+ *   Save / restore: both parameter vectors, the BatchNorm buffers, FG_GAN_OPT_STATE_D / _G and fg_gan_optimizer_steps, put back with
+ *   copies, fg_gan_set_optimizer (first), fg_gan_set_optimizer_steps and fg_gan_set_seeds, continue a run bit for bit under every rule:
+ *   fg_gan_set_optimizer_steps(n > 0) also tells SGD that its momentum buffer already holds a gradient.
+ *   fg_gan_set_optimizer in mid-run: with the rule the net already has (method unchanged) only the hyper-parameters change -- state
+ *   and step count stay; with ANOTHER rule the net's state buffer is zeroed, its step count returns to 0 and SGD's first-step rule
+ *   (the momentum buffer starts as the first gradient) is armed again. */
 enum { FG_STEP_NO_UPDATE = 1 };
 enum fg_gan_buffer_id {
     FG_GAN_D_INPUT = 0,       /* D's batch, NHWC [B][H][W][C]: real || fake (D-step), G's samples (G-step)            */
