@@ -155,7 +155,9 @@ static void make_plan(fg_net* n, int B) {
         if (s.kind == ST_BNPRELU) off += align64(2 * s.oc);
         if (s.kind == ST_JOIN)
             for (int k = 0; k < n->n_branch; ++k) { n->gsplit_off[k] = off; off += align64((long long)B * n->br_w[k]); }
-        if (s.kind == ST_BNPRELU && &s != &n->st[0] && (&s)[-1].kind == ST_CONV) {
+        // (not behind Linear + View(C, H, W): its epilogue sees rows of C * H * W features, the statistics are per channel over
+        //  B * H * W rows -- the statistics pass over the stage output runs instead)
+        if (s.kind == ST_BNPRELU && &s != &n->st[0] && (&s)[-1].kind == ST_CONV && (&s)[-1].geom.o_hw <= 1) {
             s.stats_cap = 2 * ((long long)B * s.ih * s.iw / 32 + 16) * s.ic;     // >= 2 x (wave rows of any tiling) x C
             s.stats_off = off; off += align64(s.stats_cap);
         }
@@ -439,7 +441,9 @@ static int forward_run(fg_net* n, long long* out_offset) {
                                          (train && s.x6_off >= 0) ? (void*)(ws + s.x6_off) : nullptr, &s.x6_valid,
                                          bn ? ws + bn->stats_off : nullptr, bn ? bn->stats_cap : 0, bn ? &bn->stats_rows : nullptr,
                                          pr ? &act : nullptr,
-                                         (has_next && n->st[si + 1].kind == ST_ACTPOOL && fg_fuse_prelu(ctx)) ? &n->pend : nullptr);
+                                         // (not behind Linear + View(C, H, W): its partials and its packed bias are rows of
+                                         //  C * H * W features, the pooling pass indexes the bias by channel)
+                                         (has_next && n->st[si + 1].kind == ST_ACTPOOL && fg_fuse_prelu(ctx) && g.o_hw <= 1) ? &n->pend : nullptr);
                 if (pr && !rc) pr->act_done = act.applied;
                 break;
             }
@@ -475,7 +479,7 @@ static int forward_run(fg_net* n, long long* out_offset) {
                 if (train && !sync && s.stats_rows > 0 && si > 0) {
                     const Stage& cv = n->st[si - 1];
                     a.stats_part = ws + s.stats_off; a.stats_rows = s.stats_rows;
-                    a.stats_pivot = cv.bias_packed ? cv.bias_packed : P + cv.b_off;
+                    a.stats_pivot = P + cv.b_off;        // (never a packed bias: no epilogue statistics behind Linear + View)
                 }
                 s.stats_rows = 0;
                 if (!sync) { rc = fg_launch_bn_forward(ctx, a); break; }
@@ -760,7 +764,7 @@ int fg_net_create(fg_ctx* ctx, const fg_layer_spec* L, int nl, int in_c, int in_
                 // is the module's output, like the reference's self.output), and nothing is fused across it
                 const int f = review_factor;
                 review_factor = 0;
-                if (s.has_sigmoid) { rc = fg_set_err(ctx, FG_ERR_UNSUPPORTED, "fg_net_create: layer %d: Sigmoid fused in front of the view", i); break; }
+                // (a Sigmoid behind a thin-output layer with a factor is never fused into it: FG_CONV above)
                 Stage v; v.kind = ST_REVIEW; v.first_layer = v.last_layer = i; v.factor = f;
                 v.ic = c; v.ih = h; v.iw = w; v.oc = c / (f * f); v.oh = h * f; v.ow = w * f; v.src = (int)n->st.size() - 1;
                 n->layers[i].stage = (int)n->st.size();

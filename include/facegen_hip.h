@@ -207,7 +207,28 @@ typedef struct fg_layer_spec {
  *   (FG_ERR_WORKSPACE, a bad batch, missing masks ...), failed or is still paused: the workspace then does not hold that batch's
  *   activations; fg_net_backward_range that does not start at the last stage or continue exactly where the previous call of the SAME
  *   forward stopped; fg_net_forward_resume / fg_net_backward_resume when that pass is not paused; fg_net_layer_output of the last
- *   layer while fg_net_forward_to has redirected it. */
+ *   layer while fg_net_forward_to has redirected it.
+ *
+ * WHAT IS FUSED, AND WHEN NOT (decided by fg_net_create from what stands next to what; a list that misses a precondition runs as
+ * separate stages with the same results -- tests/NET_FUSIONS.md has one small net on each side of every line):
+ *   Linear + View(C, H, W)                one stage, output written in NHWC.  Its bias gradient takes one kernel up to batch 1024 and a
+ *                                         column sum + transpose above.  A BatchNorm behind it computes its own statistics, and a
+ *                                         PReLU + SpatialDropout + AvgPool behind it does not sum its split-K partials.
+ *   View(features) + Linear               the Linear reads the map in NHWC; PReLU / Dropout / LeakyReLU may stand between the two.
+ *                                         Linear(-> 1) behind a spatial flatten is refused (FG_ERR_UNSUPPORTED).
+ *   Linear(-> 1) [+ Sigmoid]              one matrix-vector stage.
+ *   UpSamplingNearest(2) + conv           one tap-folded convolution when nIn % 4 == 0, nIn > 4, nOut > 4, k <= 5, stride 1 and no
+ *                                         factor; else the upsampled map is materialised.
+ *   conv(-> 1 | 3 | 4 planes) + Sigmoid   one stage (the layers fg_thin_layer names; not with a factor > 1: the view stands between).
+ *   BatchNorm [+ PReLU]                   one stage; directly behind a convolution or a plain Linear that did not split K (and not in
+ *                                         the bf16x6 math mode) the batch statistics come from that layer's epilogue.
+ *   PReLU + SpatialDropout + AvgPool      one stage when C % 4 == 0 and H, W are even, also as the net's first stage.
+ *   PReLU + MaxPool [+ Dropout]           one stage when C % 4 == 0, H, W are even and the PReLU is not layer 0.
+ *   PReLU [+ Dropout]                     forward: written by the producing convolution / Linear (its epilogue when it did not split
+ *                                         K and there is no mask, else the pass that sums the splits); backward: folded into the
+ *                                         layer behind it (FG_FUSE_PRELU): in that layer's epilogue where it does not split K and
+ *                                         runs an fp32 kernel, in the pass that sums its splits (any math mode, C % 4 == 0) where it
+ *                                         does; not when the PReLU is the net's first stage or the first of a ranged call. */
 int fg_net_create(fg_ctx* ctx, const fg_layer_spec* layers, int n_layers, int in_c, int in_h, int in_w, fg_net** out);
 int fg_net_destroy(fg_net* net);
 long long fg_net_num_params(const fg_net* net);   /* length of the flat parameter vector (reference order) */

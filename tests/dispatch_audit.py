@@ -2,9 +2,10 @@
 FG_LAUNCH_LOG=1 prints one line per launch, produced by the very host code that decides the launches on a device.  This module
 holds the child programs (replay of the GPU parity lists, the seeded sweep of the public conv / linear entries, one training
 iteration of the baseline nets; the strided sweep and replay of one-layer stride-2 nets; the replay of the module-level pointwise,
-BatchNorm, optimizer and RNG lists), the parser of their logs, the census of the launch sites in csrc/*.hip and the census of the
-launches with a capped grid.
-tests/test_dispatch_coverage_host.py asserts on what they return; tests/DISPATCH_COVERAGE.md is the ledger.
+BatchNorm, optimizer and RNG lists; the sweep and replay of whole layer lists from tests/net_cases.py), the parser of their logs,
+the census of the launch sites in csrc/*.hip and the census of the launches with a capped grid.
+tests/test_dispatch_coverage_host.py and tests/test_net_fusions_host.py assert on what they return; tests/DISPATCH_COVERAGE.md is
+the ledger.
 
 A launch's SIGNATURE is (launch-site text, block size, dynamic LDS bytes); the grid is left out.
 
@@ -31,6 +32,18 @@ CHANNELS = [1, 2, 3, 4, 5, 6, 8, 12, 16, 20, 32, 48, 64, 96, 128, 192, 256, 320,
 CAP = 1 << 25                      # floats per operand
 
 LAUNCH_RE = re.compile(r"^fg-launch (.*) grid=(\d+),(\d+),(\d+) block=(\d+) lds=(\d+)$")
+
+_MEMO = {}
+
+
+def memo(f):
+    """one run per process: tests/test_dispatch_coverage_host.py and tests/test_net_fusions_host.py ask for the same logs"""
+    def g():
+        if f.__name__ not in _MEMO:
+            _MEMO[f.__name__] = f()
+        return _MEMO[f.__name__]
+    g.__name__, g.__doc__ = f.__name__, f.__doc__
+    return g
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -271,6 +284,165 @@ say("fg-net end 0")
 """
 
 
+# whole layer lists (tests/net_cases.py) as compiled nets: create, forward (train), forward (evaluate), forward (train), backward with
+# flags 3, 1 and 2, then fg_net_backward_range split at every stage boundary, in a workspace of exactly fg_net_workspace_bytes.  The
+# launch log of thousands of nets is too long to hand to the parent: the child sends its own stderr to a file and prints one JSON
+# line per job with the return codes and the launch signatures (and grids) of every pass.
+NET_PASSES = ("fwd", "eval", "fwd2", "bwd3", "bwd1", "bwd2", "range")
+NET_ENGINE = ENGINE + r"""
+import ctypes, fcntl, os, tempfile
+from face_generator_amd.runtime import make_specs
+import net_cases as NC
+LOG = tempfile.NamedTemporaryFile("w+", suffix=".log", delete=False)
+# O_APPEND on the descriptor itself (mkstemp does not set it, whatever the mode string): the file is truncated after every job, and
+# without it the next write would land at the old offset behind a run of NUL bytes -- the job's first launch line would be lost
+fcntl.fcntl(LOG.fileno(), fcntl.F_SETFL, fcntl.fcntl(LOG.fileno(), fcntl.F_GETFL) | os.O_APPEND)
+ERR = os.dup(2)
+os.dup2(LOG.fileno(), 2)
+RD = open(LOG.name)
+os.unlink(LOG.name)
+def guarded(f):
+    try:
+        f()
+    except BaseException:
+        import traceback
+        os.write(ERR, traceback.format_exc().encode())
+        raise
+lib.fg_net_mask_elems.restype = ctypes.c_longlong
+def launches():
+    out = []
+    for l in RD.read().splitlines():
+        assert "\0" not in l, "a hole in the launch log"
+        if l.startswith("fg-launch "): out.append(l)
+    return out
+def run_net(job, grids=False):
+    settings(job)                       # the fusion bits are read when a net is created
+    layers, (c, hh, w), B = [NC.pad(l) for l in job["layers"]], job["dims"], job["batch"]
+    res = dict(job, rc={}, log={})
+    h, off = ctypes.c_void_p(), ctypes.c_longlong()
+    launches()
+    def done(p, rc):
+        res["rc"][p] = [rc, lib.fg_last_error(ctx.h).decode() if rc else ""]
+        res["log"].setdefault(p, []).extend(launches())
+        return rc
+    def finish():
+        os.ftruncate(LOG.fileno(), 0); RD.seek(0)
+        if not grids:
+            res["log"] = {p: sorted(set(" ".join(l.split(" grid=")[0:1] + l.split(" ")[-2:]) for l in v)) for p, v in res["log"].items()}
+        print(json.dumps(res), flush=True)
+    if done("create", lib.fg_net_create(ctx.h, make_specs(layers), len(layers), c, hh, w, ctypes.byref(h))):
+        return finish()
+    n, nbuf, ns = lib.fg_net_num_params(h), lib.fg_net_num_buffers(h), lib.fg_net_num_stages(h)
+    res["stages"] = ns
+    P, G, Bf = torch.empty(max(n, 1)), torch.empty(max(n, 1)), torch.empty(max(nbuf, 1))
+    ctx.check(lib.fg_net_bind(h, P.data_ptr(), G.data_ptr(), Bf.data_ptr()))
+    nb = lib.fg_net_workspace_bytes(h, B)
+    ws, x = torch.empty((nb + 3) // 4), torch.empty(B * c * hh * w)
+    gx = torch.empty(x.numel())
+    oc, oh, ow = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    lib.fg_net_out_dims(h, ctypes.byref(oc), ctypes.byref(oh), ctypes.byref(ow))
+    gy = torch.empty(B * oc.value * oh.value * ow.value)
+    nm = lib.fg_net_num_masks(h)
+    ms = [torch.ones(max(1, lib.fg_net_mask_elems(h, i, B))) for i in range(nm)]
+    mp = (ctypes.c_void_p * max(nm, 1))(*[m.data_ptr() for m in ms])
+    F = lambda train: lib.fg_net_forward(h, B, x.data_ptr(), ws.data_ptr(), nb, train, mp if nm else None, nm, ctypes.byref(off))
+    R = lambda fl, a, b: lib.fg_net_backward_range(h, B, x.data_ptr(), gy.data_ptr(), ws.data_ptr(), nb, fl, gx.data_ptr(), a, b)
+    ok = not done("fwd", F(1)) and not done("eval", F(0)) and not done("fwd2", F(1))
+    if ok:
+        for fl in (3, 1, 2):
+            done("bwd%%d" %% fl, R(fl, ns - 1, 0))
+        rc = 0
+        for s in range(1, ns):
+            rc = rc or R(3, ns - 1, s) or R(3, s - 1, 0)
+        done("range", rc)
+    lib.fg_net_destroy(h)
+    finish()
+"""
+
+NET_SWEEP = NET_ENGINE + r"""
+guarded(lambda: [run_net(j) for j in json.load(open(sys.argv[1]))])
+"""
+
+NET_REPLAY = NET_ENGINE + r"""
+def replay_all():
+  for c in NC.NET_CASES:
+    run_net(dict(list="NET_CASES", kind="net", case=c.name, dims=list(c.dims), layers=[list(l) for l in c.layers], batch=c.batch, math=c.math,
+                 fusion=c.fusion, shape=[]), grids=True)
+  for (name, row, dims, layers, msg) in NC.REFUSED_CASES:
+    run_net(dict(list="REFUSED_CASES", kind="net", case=name, dims=list(dims), layers=[list(l) for l in layers], batch=2, math=0,
+                 fusion=%(default)d, shape=[]))
+guarded(replay_all)
+"""
+
+
+def _parse_net_jobs(lines):
+    """JSON lines of the net children -> jobs in the shape parse_jobs gives: rc {pass: (code, message)}, sigs, grids"""
+    jobs = []
+    for l in lines:
+        if not l.startswith("{"):
+            continue
+        j = json.loads(l)
+        j["rc"] = {p: tuple(v) for p, v in j["rc"].items()}
+        j["sigs"], j["grids"] = {}, {}
+        for p, v in j.pop("log").items():
+            j["sigs"][p], j["grids"][p] = [], []
+            for line in v:
+                m = LAUNCH_RE.match(line)
+                if m:
+                    j["sigs"][p].append(sig_of(line))
+                    j["grids"][p].append((kernel_of(m.group(1)),) + tuple(int(g) for g in m.group(2, 3, 4)))
+                else:           # the sweep's compact form: "fg-launch <site> block=N lds=N"
+                    m = re.match(r"^fg-launch (.*) block=(\d+) lds=(\d+)$", line)
+                    assert m, line
+                    j["sigs"][p].append((m.group(1), int(m.group(2)), int(m.group(3))))
+        jobs.append(j)
+    return jobs
+
+
+def _run_stdout(code, args=(), out=subprocess.PIPE):
+    env = dict(os.environ, FG_LAUNCH_LOG="1", OMP_NUM_THREADS="1")     # (several children side by side: one thread each)
+    fmt = dict(root=ROOT, tests=os.path.join(ROOT, "tests"), default=FG_FUSE_DEFAULT)
+    return subprocess.Popen([sys.executable, "-c", code % fmt] + list(args), env=env, stdout=out, stderr=subprocess.PIPE, text=True)
+
+
+@memo
+def net_replay():
+    """NET_CASES and REFUSED_CASES of tests/net_cases.py under each case's own settings -> parsed jobs (full launch lines)"""
+    p = _run_stdout(NET_REPLAY)
+    out, err = p.communicate(timeout=600)
+    assert p.returncode == 0, err[-3000:]
+    return _parse_net_jobs(out.splitlines())
+
+
+def net_sweep(n=None, workers=None):
+    """every generated layer list x {fusion 503, 23, 502} x {math 0, 6} -> parsed jobs (unique signatures per pass, no grids)"""
+    import tempfile
+    import net_cases as NC
+    lists = NC.random_layer_lists(NC.SWEEP_SEED, NC.SWEEP_N if n is None else n)
+    jobs = [dict(list="net-sweep", kind="net", idx=i, dims=list(d), layers=[list(l) for l in L], batch=B, math=m, fusion=f, shape=[])
+            for i, (d, L, B) in enumerate(lists) for f in NC.FUSIONS for m in NC.MATHS]
+    workers = workers or max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4))
+    files, procs = [], []
+    try:
+        for k in range(workers):
+            f = tempfile.NamedTemporaryFile("w", suffix=".json", delete=False)
+            json.dump(jobs[k::workers], f); f.close()
+            o = tempfile.NamedTemporaryFile("w+", suffix=".out", delete=False)     # (a file, not a pipe: nobody reads until the end)
+            files += [f.name, o.name]
+            procs.append((_run_stdout(NET_SWEEP, [f.name], out=o), o))
+        res = []
+        for p, o in procs:
+            _, err = p.communicate(timeout=900)
+            assert p.returncode == 0, err[-3000:]
+            o.seek(0)
+            res += _parse_net_jobs(o.read().splitlines())
+            o.close()
+    finally:
+        for f in files:
+            os.unlink(f)
+    return sorted(res, key=lambda j: (j["idx"], j["fusion"], j["math"]))
+
+
 def reclassified_net_launches():
     """{tag: [launch line, ...]} of forward + backward of the nets above, planning-only"""
     return _split_nets(_run(RECLASSIFIED), "1")
@@ -314,6 +486,7 @@ def all_sigs(jobs):
     return {s for j in jobs for v in j["sigs"].values() for s in v}
 
 
+@memo
 def replay():
     """the GPU parity lists under the tests' own settings -> parsed jobs"""
     return parse_jobs(_run(REPLAY))
@@ -417,11 +590,13 @@ def strided_sweep(extra=()):
     return _run_jobs(STRIDED, jobs)
 
 
+@memo
 def pointwise_replay():
     """CAP_CASES, BN_CASES, OPT_CASES and RNG_CASES of tests/test_gpu_pointwise_paths.py -> parsed jobs (one pass, "run")"""
     return parse_jobs(_run(POINTWISE_REPLAY))
 
 
+@memo
 def strided_replay():
     """STRIDED_CASES of tests/test_gpu_strided_conv.py under that module's settings"""
     return parse_jobs(_run(STRIDED_REPLAY))

@@ -86,3 +86,53 @@ def oracle_backward_on_device_branches(ctx, dn, net, x, gy, gflat=None, max_flip
         adopt_device_branches(ctx, dn, net, clear=True)
     assert flips <= max(1, max_flip_frac * units), "%d of %d PReLU decisions adopted from the device differ from the oracle's" % (flips, units)
     return gin
+
+
+def assert_net_bars(what, D, y, out, gx, gin, got):
+    """The project's net-level bars (tests/test_gpu_net.py:279-297): outputs 1e-5; input gradient 1e-4 max|g| + 1e-7; every parameter
+    tensor's gradient 1e-4 max|g_tensor| + 1e-7 (a PReLU slope: + 32 x 6e-8 x the conditioning of its sum), floored at 2e-6 max|g_net|.
+    D: the oracle after its backward; y, gx, got: the device's output, input gradient (both shaped like the oracle's) and flat
+    parameter gradient."""
+    from oracle import torch7_nn as O
+    e_out = np.abs(y - out).max()
+    e_in = np.abs(gx - gin).max()
+    print("%s: output err %.3e (bar 1e-5); input-gradient err %.3e (bar %.3e)" % (what, e_out, e_in, 1e-4 * np.abs(gin).max() + 1e-7))
+    ref = np.concatenate([getattr(m, gn).reshape(-1) for (m, pn, gn) in D.parameters()]) if D.parameters() else np.zeros(0)
+    off, gmax, rows = 0, (np.abs(ref).max() if ref.size else 0.0), []
+    for (m, pn, gn) in D.parameters():
+        r = getattr(m, gn).reshape(-1)
+        e = np.abs(got[off:off + r.size] - r).max()
+        tol = 1e-4 * np.abs(r).max() + 1e-7 + (32 * 6e-8 * getattr(m, "gw_cond", 0.0) if isinstance(m, O.PReLU) else 0.0)
+        tol = max(tol, 2e-6 * gmax)
+        rows.append((e / tol, "%s %s.%s @%d: err %.3e tol %.3e (max|g_tensor| %.3e, max|g_net| %.3e)" % (what, type(m).__name__, pn, off, e, tol, np.abs(r).max(), gmax)))
+        off += r.size
+    if rows:
+        print("%s: worst parameter tensor: %s" % (what, max(rows)[1]))
+    close(y, out, atol=1e-5, what=what + " outputs")
+    close(gx, gin, atol=1e-4 * np.abs(gin).max() + 1e-7, what=what + " input gradient")
+    bad = [r[1] for r in rows if r[0] > 1]
+    assert not bad, "\n".join(bad)
+
+
+def forward_backward_against_oracle(ctx, what, D, Dd, dims, B, rng, masks):
+    """a compiled net (Dd, face_generator_amd.nn) against its float32 oracle D: train forward, backward, evaluate forward"""
+    from oracle import torch7_nn as O
+    pD, gD = D.getParameters()
+    p, g = Dd.getParameters()
+    assert p.numel() == pD.size
+    p.copy_(torch.tensor(pD)); Dd.device_net.params_changed()
+    if masks:
+        O.set_dropout_masks(D, masks)
+    x = rng.uniform(0, 1, (B,) + tuple(dims)).astype(np.float32)
+    out = D.forward(x)
+    gy = rng.standard_normal(out.shape).astype(np.float32)
+    gD[...] = 0
+    gin = D.backward(x, gy)
+    dm = [dev(m.reshape(-1), ctx.device) for m in masks]
+    y = Dd.device_net.forward(nhwc(x, ctx.device), masks=dm or None, train=True)
+    gx = Dd.device_net.backward(dev(gy, ctx.device), param_grads=True, input_grad=True)
+    assert_net_bars(what, D, y.cpu().numpy().reshape(out.shape), out, nchw(gx), gin, g.cpu().numpy())
+    D.evaluate(); Dd.evaluate()
+    close(Dd.device_net.forward(nhwc(x, ctx.device)).cpu().numpy().reshape(out.shape), D.forward(x), atol=1e-5, what=what + " evaluate")
+    D.training(); Dd.training()
+    return x, gy, dm

@@ -11,6 +11,7 @@ import torch
 
 from oracle import torch7_nn as O
 from gpu_util import nhwc, nchw, dev, close, close_after_first_adam_step
+from gpu_util import forward_backward_against_oracle as _forward_backward_against_oracle
 from test_gpu_net import _fill_nontrivial
 from test_gpu_baseline_sizes import check_every_tensor, assert_flips_bounded, f64_state, floor_for, adam_from
 from test_gpu_train_epoch import ListDataset, Recorder, load_state
@@ -99,44 +100,6 @@ def test_chain_of_the_new_channel_counts(ctx, C):
 
 def _masks_for(dn, B, rng):
     return [(rng.random((B, dn.mask_shape(i, B)[0] // B)) < 0.5).astype(np.float32) for i in range(dn.n_masks)]
-
-
-def _forward_backward_against_oracle(ctx, what, D, Dd, dims, B, rng, masks):
-    pD, gD = D.getParameters()
-    p, g = Dd.getParameters()
-    assert p.numel() == pD.size
-    p.copy_(torch.tensor(pD)); Dd.device_net.params_changed()
-    if masks:
-        O.set_dropout_masks(D, masks)
-    x = rng.uniform(0, 1, (B,) + tuple(dims)).astype(np.float32)
-    out = D.forward(x)
-    gy = rng.standard_normal(out.shape).astype(np.float32)
-    gD[...] = 0
-    gin = D.backward(x, gy)
-    dm = [dev(m.reshape(-1), ctx.device) for m in masks]
-    y = Dd.device_net.forward(nhwc(x, ctx.device), masks=dm or None, train=True)
-    e_out = np.abs(y.cpu().numpy().reshape(out.shape) - out).max()
-    gx = Dd.device_net.backward(dev(gy, ctx.device), param_grads=True, input_grad=True)
-    e_in = np.abs(nchw(gx) - gin).max()
-    print("%s: output err %.3e (bar 1e-5); input-gradient err %.3e (bar %.3e)" % (what, e_out, e_in, 1e-4 * np.abs(gin).max() + 1e-7))
-    got, ref = g.cpu().numpy(), gD
-    off, gmax, rows = 0, np.abs(ref).max(), []
-    for (m, pn, gn) in D.parameters():
-        r = getattr(m, gn).reshape(-1)
-        e = np.abs(got[off:off + r.size] - r).max()
-        tol = 1e-4 * np.abs(r).max() + 1e-7 + (32 * 6e-8 * getattr(m, "gw_cond", 0.0) if isinstance(m, O.PReLU) else 0.0)
-        tol = max(tol, 2e-6 * gmax)
-        rows.append((e / tol, "%s %s.%s @%d: err %.3e tol %.3e (max|g_tensor| %.3e, max|g_net| %.3e)" % (what, type(m).__name__, pn, off, e, tol, np.abs(r).max(), gmax)))
-        off += r.size
-    print("%s: worst parameter tensor: %s" % (what, max(rows)[1]))
-    close(y.cpu().numpy().reshape(out.shape), out, atol=1e-5, what=what + " outputs")
-    close(nchw(gx), gin, atol=1e-4 * np.abs(gin).max() + 1e-7, what=what + " input gradient")
-    bad = [r[1] for r in rows if r[0] > 1]
-    assert not bad, "\n".join(bad)
-    D.evaluate(); Dd.evaluate()
-    close(Dd.device_net.forward(nhwc(x, ctx.device)).cpu().numpy().reshape(out.shape), D.forward(x), atol=1e-5, what=what + " evaluate")
-    D.training(); Dd.training()
-    return x, gy, dm
 
 
 # ---- item 5 ----------------------------------------------------------------------------------------------------------------------
