@@ -289,7 +289,7 @@ struct fg_gan {
     int pendingD = 0;                  // D's gradient all-reduce is in flight, its update is deferred
     int grads_local[2] = {0, 0};       // a NO_UPDATE step left un-reduced gradients for fg_gan_update
     long long d_out_off = 0;
-    int last_B[2] = {0, 0};
+    int last_B = 0;                    // batch of the last closure, D-step or G-step: the count of FG_GAN_D_OUTPUT
     std::vector<GBucket> buckets;
     bool sync_bn = false;
     int overlap = 1;                   // 2 (test hook): take the N > 1 exchange path even on a one-rank communicator
@@ -347,13 +347,12 @@ static int gan_world(const fg_gan* g) { return g->comm ? g->comm->world : 1; }
 static bool gan_exchange(const fg_gan* g) { return g->comm && (g->comm->world > 1 || g->overlap == 2); }
 
 // sync-BN: run a forward / backward to completion through its pauses (one fp64 all-reduce per BatchNorm)
-static int gan_drain(fg_gan* g, fg_net* n, int rc, bool fwd) {
+static int gan_drain(fg_gan* g, fg_net* n, int rc, bool fwd, long long* out_off = nullptr) {
     while (rc == FG_PAUSED_SYNC) {
         if (!g->comm) return fg_set_err(g->ctx, FG_ERR_INVALID, "fg_gan: sync-BN without a communicator");
         int r = fg_allreduce_sum_f64(g->comm, (double*)(g->ws + g->o_sync), (size_t)fg_net_sync_count(n));
         if (r) return r;
-        long long off = 0;
-        rc = fwd ? fg_net_forward_resume(n, &off) : fg_net_backward_resume(n);
+        rc = fwd ? fg_net_forward_resume(n, out_off) : fg_net_backward_resume(n);      // (a paused forward reports its output only here)
     }
     return rc;
 }
@@ -435,7 +434,9 @@ static int gan_targets(fg_gan* g, int w, int B) {
     return FG_OK;
 }
 
-// noise batch (when the caller passes none) + every dropout mask (ditto) of one closure in a single Philox launch
+// noise batch (when the caller passes none) + every dropout mask (ditto) of one closure in a single Philox launch -- up to
+// FG_RNG_MAX_SEGS segments; a closure that draws more takes one launch per FG_RNG_MAX_SEGS of them.  A segment's bits depend on its
+// own (seed, offset) alone, never on which launch carries it.
 static int gan_draw(fg_gan* g, int n_noise_rows, const float* noise_in, int B, const float* const* masks_in,
                     const float** noise_out, std::vector<const float*>& dmasks) {
     RngMulti m; memset(&m, 0, sizeof(m));
@@ -451,7 +452,11 @@ static int gan_draw(fg_gan* g, int n_noise_rows, const float* noise_in, int B, c
     dmasks.assign(nm, nullptr);
     for (int i = 0; i < nm; ++i) {
         if (masks_in) { dmasks[i] = masks_in[i]; continue; }
-        if (m.n >= FG_RNG_MAX_SEGS) return fg_set_err(g->ctx, FG_ERR_UNSUPPORTED, "fg_gan: more than %d random segments per step", FG_RNG_MAX_SEGS);
+        if (m.n >= FG_RNG_MAX_SEGS) {
+            int rc = fg_launch_rng_multi(g->ctx, m);
+            if (rc) return rc;
+            memset(&m, 0, sizeof(m));
+        }
         RngSeg& s = m.seg[m.n++];
         s.out = g->ws + g->o_mask[0][i]; s.n = fg_net_mask_elems(g->D, i, B); s.seed = g->mask_seed; s.offset = g->mask_off;
         s.lo = fg_net_mask_keep(g->D, i); s.hi = 0.f; s.mode = 1;
@@ -512,6 +517,13 @@ int fg_gan_create(fg_ctx* ctx, fg_net* G, fg_net* D, int table_inputs, int max_b
 
 int fg_gan_destroy(fg_gan* g) { delete g; return FG_OK; }
 
+/* test hook: re-cut the buckets of G's overlapped backward at `floats` parameters each (fg_gan_create: 900000) */
+int fg_test_set_gan_bucket_target(fg_gan* g, long long floats) {
+    if (!g || floats < 1) return fg_set_err(g ? g->ctx : nullptr, FG_ERR_INVALID, "fg_test_set_gan_bucket_target: bad argument");
+    gan_buckets(g, floats);
+    return FG_OK;
+}
+
 /* the nets' own workspaces (fg_net_workspace_bytes(net, max_batch)); re-bind whenever the caller re-allocates them */
 int fg_gan_bind_workspaces(fg_gan* g, void* wsG, size_t wsG_bytes, void* wsD, size_t wsD_bytes) {
     if (!g || !wsG || !wsD) return fg_set_err(g ? g->ctx : nullptr, FG_ERR_INVALID, "fg_gan_bind_workspaces: null argument");
@@ -531,6 +543,12 @@ int fg_gan_set_comm(fg_gan* g, fg_comm* comm, int sync_bn, int overlap) {
     return FG_OK;
 }
 
+int fg_gan_get_offsets(const fg_gan* g, long long* noise_offset, long long* mask_offset) {
+    if (!g) return FG_ERR_INVALID;
+    if (noise_offset) *noise_offset = (long long)g->noise_off;
+    if (mask_offset) *mask_offset = (long long)g->mask_off;
+    return FG_OK;
+}
 int fg_gan_set_seeds(fg_gan* g, uint64_t noise_seed, uint64_t noise_offset, uint64_t mask_seed, uint64_t mask_offset) {
     if (!g) return FG_ERR_INVALID;
     g->noise_seed = noise_seed; g->noise_off = noise_offset; g->mask_seed = mask_seed; g->mask_off = mask_offset;
@@ -575,7 +593,7 @@ int fg_gan_buffer(const fg_gan* g, int what, long long* offset_floats, long long
         case FG_GAN_CONFUSION: o = g->o_conf; c = 8; break;
         case FG_GAN_OPT_STATE_D: o = g->o_opt[0]; c = 2 * g->nP[0]; break;
         case FG_GAN_OPT_STATE_G: o = g->o_opt[1]; c = 2 * g->nP[1]; break;
-        case FG_GAN_D_OUTPUT: o = g->d_out_off; c = g->last_B[0] > g->last_B[1] ? g->last_B[0] : g->last_B[1]; break;
+        case FG_GAN_D_OUTPUT: o = g->d_out_off; c = g->last_B; break;
         case FG_GAN_D_MASKS: o = g->o_mask[0].empty() ? 0 : g->o_mask[0][0]; c = g->o_targets - o; break;
         case FG_GAN_SYNC_BUF: o = g->o_sync; c = g->total - g->o_sync; break;
         default: return fg_set_err(g->ctx, FG_ERR_INVALID, "fg_gan_buffer: unknown buffer %d", what);
@@ -598,10 +616,9 @@ static int gan_check_step(fg_gan* g, int B, const char* who) {
     return FG_OK;
 }
 
-int fg_step_D(fg_gan* g, int B, const float* real, const float* cond_real, const float* cond_fake, const float* noise,
-              const float* const* masks, int flags) {
-    int rc = gan_check_step(g, B, "fg_step_D");
-    if (rc) return rc;
+static int gan_step_D(fg_gan* g, int B, const float* real, const float* cond_real, const float* cond_fake, const float* noise,
+                      const float* const* masks, int flags) {
+    int rc;
     fg_ctx* ctx = g->ctx;
     if (!real || (g->table && (!cond_real || !cond_fake))) return fg_set_err(ctx, FG_ERR_INVALID, "fg_step_D: null input");
     const int h = B / 2;
@@ -617,8 +634,13 @@ int fg_step_D(fg_gan* g, int B, const float* real, const float* cond_real, const
     }
     long long off = 0;
     // C5: the fakes come from G in TRAIN mode (BatchNorm batch statistics over B/2; running statistics move)
-    rc = fg_net_forward_to(g->G, h, gin, g->wsG, g->wsG_bytes, 1, nullptr, 0, &off, dinput + (long long)h * g->img);
-    if ((rc = gan_drain(g, g->G, rc, true))) return rc;
+    // G's last stage writes straight into the second half of D's batch where that half starts on 16 bytes ((B/2) * C*H*W % 4 == 0);
+    // elsewhere G keeps its output and copy_kernel, which takes any alignment, places it
+    float* fake = dinput + (long long)h * g->img;
+    const bool direct = ((uintptr_t)fake & 15) == 0;
+    rc = fg_net_forward_to(g->G, h, gin, g->wsG, g->wsG_bytes, 1, nullptr, 0, &off, direct ? fake : nullptr);
+    if ((rc = gan_drain(g, g->G, rc, true, &off))) return rc;
+    if (!direct && (rc = fg_launch_copy(ctx, g->wsG + off, fake, (long long)h * g->img))) return rc;
     const float* din = dinput;
     if (g->table) {                      // nn.CAddTable{x, cond} (models_c2f.lua:240) over [real | fake] x [cond_real | cond_fake]
         if ((rc = fg_launch_add_halves(ctx, real, cond_real, dinput + (long long)h * g->img, cond_fake, g->ws + g->o_dsum,
@@ -627,8 +649,8 @@ int fg_step_D(fg_gan* g, int B, const float* real, const float* cond_real, const
     } else if ((rc = fg_launch_copy(ctx, real, dinput, (long long)h * g->img))) return rc;
     if ((rc = gan_targets(g, 0, B))) return rc;
     rc = fg_net_forward(g->D, B, din, g->wsD, g->wsD_bytes, 1, dm.empty() ? nullptr : dm.data(), (int)dm.size(), &off);
-    if ((rc = gan_drain(g, g->D, rc, true))) return rc;
-    g->d_out_off = off; g->last_B[0] = B;
+    if ((rc = gan_drain(g, g->D, rc, true, &off))) return rc;
+    g->d_out_off = off; g->last_B = B;
     int* conf = (int*)(g->ws + g->o_conf);
     if ((rc = fg_launch_bce(ctx, g->wsD + off, g->ws + g->o_targets, g->ws + g->o_loss, g->ws + g->o_dprob, conf, B))) return rc;
     g->grads_local[0] = 0;      // the backward below overwrites what an earlier FG_STEP_NO_UPDATE step held for fg_gan_update
@@ -645,9 +667,8 @@ int fg_step_D(fg_gan* g, int B, const float* real, const float* cond_real, const
     return gan_schedule_update_D(g);
 }
 
-int fg_step_G(fg_gan* g, int B, const float* cond, const float* noise, const float* const* masks, int flags) {
-    int rc = gan_check_step(g, B, "fg_step_G");
-    if (rc) return rc;
+static int gan_step_G(fg_gan* g, int B, const float* cond, const float* noise, const float* const* masks, int flags) {
+    int rc;
     fg_ctx* ctx = g->ctx;
     if (g->table && !cond) return fg_set_err(ctx, FG_ERR_INVALID, "fg_step_G: null input");
     const float* nz = nullptr;
@@ -661,7 +682,7 @@ int fg_step_G(fg_gan* g, int B, const float* cond, const float* noise, const flo
     }
     long long off = 0;
     rc = fg_net_forward_to(g->G, B, gin, g->wsG, g->wsG_bytes, 1, nullptr, 0, &off, dinput);
-    if ((rc = gan_drain(g, g->G, rc, true))) return rc;
+    if ((rc = gan_drain(g, g->G, rc, true, &off))) return rc;
     if ((rc = gan_finish_pending(g))) return rc;   // D's deferred update must land before D is evaluated
     const float* din = dinput;
     if (g->table) {
@@ -670,8 +691,8 @@ int fg_step_G(fg_gan* g, int B, const float* cond, const float* noise, const flo
     }
     if ((rc = gan_targets(g, 1, B))) return rc;
     rc = fg_net_forward(g->D, B, din, g->wsD, g->wsD_bytes, 1, dm.empty() ? nullptr : dm.data(), (int)dm.size(), &off);
-    if ((rc = gan_drain(g, g->D, rc, true))) return rc;
-    g->d_out_off = off; g->last_B[1] = B;
+    if ((rc = gan_drain(g, g->D, rc, true, &off))) return rc;
+    g->d_out_off = off; g->last_B = B;
     if ((rc = fg_launch_bce(ctx, g->wsD + off, g->ws + g->o_targets + g->maxB, g->ws + g->o_loss + 1, g->ws + g->o_dprob, nullptr, B))) return rc;
     // MODEL_D.modules[1].gradInput (adversarial.lua:210); D's weight gradients are not formed (quirk C6)
     float* gx = g->ws + g->o_gx;
@@ -699,6 +720,26 @@ int fg_step_G(fg_gan* g, int B, const float* cond, const float* noise, const flo
     if (!update) { g->grads_local[1] = 1; return FG_OK; }
     if (gan_exchange(g) && (rc = fg_allreduce_sum(g->comm, gG, (size_t)g->nP[1]))) return rc;
     return gan_optimize(g, 1);
+}
+
+// A step that is refused leaves the random streams where they were: the offsets gan_draw advanced are put back, so the next accepted
+// step draws what it would have drawn had the refused call never been made.
+int fg_step_D(fg_gan* g, int B, const float* real, const float* cond_real, const float* cond_fake, const float* noise,
+              const float* const* masks, int flags) {
+    int rc = gan_check_step(g, B, "fg_step_D");
+    if (rc) return rc;
+    const uint64_t noise_off = g->noise_off, mask_off = g->mask_off;
+    rc = gan_step_D(g, B, real, cond_real, cond_fake, noise, masks, flags);
+    if (rc != FG_OK) { g->noise_off = noise_off; g->mask_off = mask_off; }
+    return rc;
+}
+int fg_step_G(fg_gan* g, int B, const float* cond, const float* noise, const float* const* masks, int flags) {
+    int rc = gan_check_step(g, B, "fg_step_G");
+    if (rc) return rc;
+    const uint64_t noise_off = g->noise_off, mask_off = g->mask_off;
+    rc = gan_step_G(g, B, cond, noise, masks, flags);
+    if (rc != FG_OK) { g->noise_off = noise_off; g->mask_off = mask_off; }
+    return rc;
 }
 
 /* the optimizer step a FG_STEP_NO_UPDATE closure left out (interruptable_optimizers.lua:60-66: not calling it IS the

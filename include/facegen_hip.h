@@ -351,9 +351,13 @@ int fg_comm_schedule(fg_comm* comm, char* buf, size_t len, int reset);
  *                  D{x, cond} (CAddTable); cond_* are device NHWC.
  *      The nets are fg_net objects bound to their flat vectors (fg_net_bind); their workspaces are the caller's
  *      (fg_gan_bind_workspaces: fg_net_workspace_bytes(net, max_batch) each) plus one workspace of the step object itself.
- *      noise / masks == NULL: drawn by the library, all of a closure in one Philox launch (fg_gan_set_seeds); otherwise
+ *      noise / masks == NULL: drawn by the library, all of a closure in one Philox launch up to 12 segments (the noise and one
+ *      per dropout layer of D; one more launch per further 12), keyed by fg_gan_set_seeds; otherwise
  *      noise = device [rows][noiseDim] (table mode [rows][S][S][1]), masks = fg_net_num_masks(D) device pointers.
  *      FG_STEP_NO_UPDATE: stop before the optimizer (gradients stay in the bound gradient vector, un-reduced);
+ *      The second half of D's batch in a D-step is G's output: G's last stage writes it in place where (B/2) * C*H*W is a multiple
+ *      of 4 (that half then starts on 16 bytes); at any other size G keeps its output and one copy places it.  Every even batch
+ *      from 2 to max_batch is steppable at every image size.
  *      fg_gan_update applies it later -- the maxAccuracyD gate of adversarial.lua:124-178 reads the confusion counts in
  *      between (FG_GAN_CONFUSION: int[0..3] this rank, int[4..7] the global batch, both [pred*2 + target]); never calling
  *      fg_gan_update IS interruptableAdam's false,false path.
@@ -371,7 +375,10 @@ int fg_comm_schedule(fg_comm* comm, char* buf, size_t len, int reset);
  *   applied.  FG_GAN_CONFUSION int[4..7] (the global batch) is written by FG_STEP_NO_UPDATE D-steps only: it is the gate's input and
  *   keeps the counts of the last gated step through plain ones.
  *   Library-drawn noise and masks: every draw of `count` floats advances its offset by ceil(count / 4), the noise of a closure being
- *   fg_rng_uniform(noise_seed, noise_offset, count, -1, 1); explicit noise / masks leave the offsets alone.
+ *   fg_rng_uniform(noise_seed, noise_offset, count, -1, 1); explicit noise / masks leave the offsets alone.  A step that is REFUSED
+ *   (an odd batch, one above max_batch, a null input, a bound workspace that is too small, ...) leaves both offsets where they were,
+ *   whether or not it had drawn already: the next accepted step gives the bits it would have given without the refused call.
+ *   fg_gan_get_offsets reads them.
  *   Save / restore: both parameter vectors, the BatchNorm buffers, FG_GAN_OPT_STATE_D / _G and fg_gan_optimizer_steps, put back with
  *   copies, fg_gan_set_optimizer (first), fg_gan_set_optimizer_steps and fg_gan_set_seeds, continue a run bit for bit under every rule:
  *   fg_gan_set_optimizer_steps(n > 0) also tells SGD that its momentum buffer already holds a gradient.
@@ -387,7 +394,8 @@ enum fg_gan_buffer_id {
     FG_GAN_CONFUSION = 4,     /* int[8] (same storage as floats): local counts, global counts (0 until a D-step ran)  */
     FG_GAN_OPT_STATE_D = 5,   /* 2 * nparams(D): Adam m | v   (SGD: momentum buffer; Adagrad: variance)                */
     FG_GAN_OPT_STATE_G = 6,
-    FG_GAN_D_OUTPUT = 7,      /* D's probabilities [B] of the last closure; offset relative to D's OWN workspace       */
+    FG_GAN_D_OUTPUT = 7,      /* D's probabilities [B] of the last closure (count = ITS batch, whichever kind it was); offset
+                                 relative to D's OWN workspace                                                         */
     FG_GAN_D_MASKS = 8,       /* dropout masks the library drew (fg_gan_mask_offset per mask)                          */
     FG_GAN_SYNC_BUF = 9       /* sync-BN exchange buffer (doubles; count is in floats): what fg_gan_set_comm bound to both nets */
 };
@@ -398,6 +406,7 @@ int fg_gan_destroy(fg_gan* gan);
 int fg_gan_bind_workspaces(fg_gan* gan, void* wsG, size_t wsG_bytes, void* wsD, size_t wsD_bytes);
 int fg_gan_set_comm(fg_gan* gan, fg_comm* comm, int sync_bn, int overlap);
 int fg_gan_set_seeds(fg_gan* gan, uint64_t noise_seed, uint64_t noise_offset, uint64_t mask_seed, uint64_t mask_offset);
+int fg_gan_get_offsets(const fg_gan* gan, long long* noise_offset, long long* mask_offset);  /* where the next draws start */
 int fg_gan_set_penalty(fg_gan* gan, int which, float l1, float l2, float clamp);             /* which: 0 = D, 1 = G */
 /* method 0 adam / 1 sgd / 2 adagrad (OPT.*_optmethod); lr < 0: the rule's default (1e-3); dampening < 0: = momentum */
 int fg_gan_set_optimizer(fg_gan* gan, int which, int method, double lr, double beta1, double beta2, double eps,
@@ -413,6 +422,9 @@ int fg_step_G(fg_gan* gan, int batch, const float* cond, const float* noise, con
 int fg_gan_update(fg_gan* gan, int which);
 int fg_gan_finish_pending(fg_gan* gan);
 int fg_gan_pending(const fg_gan* gan);   /* 1 while D's update is deferred behind its gradient all-reduce */
+/* test hook: G's overlapped backward exchanges its gradient in buckets of about 900000 parameters, cut at stage boundaries from the
+ * last stage to the first; this re-cuts them at `floats` each, so that a small G has more than one */
+int fg_test_set_gan_bucket_target(fg_gan* gan, long long floats);
 
 /* ---- sampler level: sample.lua:80-89 and NN_UTILS.visualizeProgress (nn_utils.lua:131-204) as device-resident entries ----
  * Two module-level operations, usable alone, and one object built from them.

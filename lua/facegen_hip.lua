@@ -118,6 +118,7 @@ int fg_gan_destroy(fg_gan* gan);
 int fg_gan_bind_workspaces(fg_gan* gan, void* wsG, size_t wsG_bytes, void* wsD, size_t wsD_bytes);
 int fg_gan_set_comm(fg_gan* gan, fg_comm* comm, int sync_bn, int overlap);
 int fg_gan_set_seeds(fg_gan* gan, uint64_t noise_seed, uint64_t noise_offset, uint64_t mask_seed, uint64_t mask_offset);
+int fg_gan_get_offsets(const fg_gan* gan, long long* noise_offset, long long* mask_offset);
 int fg_gan_set_penalty(fg_gan* gan, int which, float l1, float l2, float clamp);
 int fg_gan_set_optimizer(fg_gan* gan, int which, int method, double lr, double beta1, double beta2, double eps, double momentum, double dampening, double weight_decay, double lr_decay, int nesterov);
 int fg_gan_optimizer_steps(const fg_gan* gan, int which);
@@ -129,6 +130,7 @@ int fg_step_G(fg_gan* gan, int batch, const float* cond, const float* noise, con
 int fg_gan_update(fg_gan* gan, int which);
 int fg_gan_finish_pending(fg_gan* gan);
 int fg_gan_pending(const fg_gan* gan);
+int fg_test_set_gan_bucket_target(fg_gan* gan, long long floats);
 enum fg_sampler_buffer_id { FG_SAMPLER_NOISE = 0, FG_SAMPLER_IMAGES = 1, FG_SAMPLER_PREDS = 2, FG_SAMPLER_ORDER_DESC = 3, FG_SAMPLER_ORDER_ASC = 4 };
 size_t fg_rank_scores_workspace_bytes(int n);
 int fg_rank_scores(fg_ctx* ctx, const float* scores, int n, int ascending, int* order_out, void* scratch, size_t scratch_bytes);

@@ -819,6 +819,29 @@ def return_codes(env):
     out["fg_gan_update(D) a second time"] = lib.fg_gan_update(r.gan.h, 0)
     r.step_D(1, flags=1); r.step_D(2)
     out["fg_gan_update(D) behind a normal step that overwrote the held gradients"] = lib.fg_gan_update(r.gan.h, 0)
+    # refused steps: the codes, and the offsets of the random streams behind them (noise and masks NULL: the library draws)
+    r = Rig(env, "px32")
+    g, real = r.gan, env.ctx.uniform((r.B // 2, r.dnD.in_h, r.dnD.in_w, r.dnD.in_c), 0.0, 1.0, seed=9)
+    g._bind()
+    D = lambda B, x=real: lib.fg_step_D(g.h, B, x.data_ptr() if x is not None else None, None, None, None, None, 0)
+    G = lambda B: lib.fg_step_G(g.h, B, None, None, None, 0)
+
+    def offsets():
+        a, b = ctypes.c_longlong(), ctypes.c_longlong()
+        env.ctx.check(lib.fg_gan_get_offsets(g.h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+    env.ctx.check(D(r.B)); env.ctx.check(G(r.B))
+    before = offsets()
+    out["fg_step_D at an odd batch"] = D(r.B - 1)
+    out["fg_step_G above max_batch"] = G(r.B + 2)
+    out["fg_step_D with a null real"] = D(r.B, None)
+    key = g._bound
+    env.ctx.check(lib.fg_gan_bind_workspaces(g.h, key[0], key[1] * 4, key[2], 4096))
+    out["FG_ERR_WORKSPACE: fg_step_D behind its draw, D's workspace bound too small"] = D(r.B)
+    out["FG_ERR_WORKSPACE: fg_step_G behind its draw, D's workspace bound too small"] = G(r.B)
+    env.ctx.check(lib.fg_gan_bind_workspaces(g.h, *[k * (4 if i % 2 else 1) for i, k in enumerate(key)]))
+    out["FG_OK: the offsets of the random streams behind five refused steps are those in front of them"] = 0 if (offsets() == before and before[0] > 0 and before[1] > 0) else -1
+    out["FG_OK: fg_step_D once its workspaces are bound again"] = D(r.B)
     return out
 
 

@@ -2,9 +2,10 @@
 FG_LAUNCH_LOG=1 prints one line per launch, produced by the very host code that decides the launches on a device.  This module
 holds the child programs (replay of the GPU parity lists, the seeded sweep of the public conv / linear entries, one training
 iteration of the baseline nets; the strided sweep and replay of one-layer stride-2 nets; the replay of the module-level pointwise,
-BatchNorm, optimizer and RNG lists; the sweep and replay of whole layer lists from tests/net_cases.py), the parser of their logs,
+BatchNorm, optimizer and RNG lists; the sweep and replay of whole layer lists from tests/net_cases.py and of whole G / D pairs at the
+step level from tests/gan_cases.py), the parser of their logs,
 the census of the launch sites in csrc/*.hip and the census of the launches with a capped grid.
-tests/test_dispatch_coverage_host.py and tests/test_net_fusions_host.py assert on what they return; tests/DISPATCH_COVERAGE.md is
+tests/test_dispatch_coverage_host.py, tests/test_net_fusions_host.py and tests/test_gan_steps_host.py assert on what they return; tests/DISPATCH_COVERAGE.md is
 the ledger.
 
 A launch's SIGNATURE is (launch-site text, block size, dynamic LDS bytes); the grid is left out.
@@ -373,6 +374,218 @@ def replay_all():
                  fusion=%(default)d, shape=[]))
 guarded(replay_all)
 """
+
+
+# whole G / D pairs (tests/gan_cases.py) at the step level: both nets and the step object created with workspaces of exactly
+# fg_net_workspace_bytes / fg_gan_workspace_bytes, then per batch and per way of giving noise and masks (NULL: drawn by the library;
+# explicit) fg_step_D, fg_step_G, fg_step_D | FG_STEP_NO_UPDATE + fg_gan_update(0), fg_step_G | FG_STEP_NO_UPDATE + fg_gan_update(1).
+# A pass is named "<closure>@<batch><n|x>"; a replayed case also runs the scenarios of tests/test_gan_steps_host.py (c), (d) and the
+# bucketed backward of its generator on transport-less communicators.
+GAN_CLOSURES = ("D", "G", "Dn", "uD", "Gn", "uG")
+GAN_ENGINE = NET_ENGINE + r"""
+import re
+import gan_cases as GC
+from face_generator_amd.runtime import DeviceNet, FusedGan
+lib.fg_net_mask_elems.restype = ctypes.c_longlong
+
+class Pair:
+    def __init__(self, job):
+        self.job, self.table, self.maxB = job, job["table"], job["max_batch"]
+        self.dnG = DeviceNet(ctx, [NC.pad(l) for l in job["glayers"]], tuple(job["gdims"]), self.maxB)
+        self.dnD = DeviceNet(ctx, [NC.pad(l) for l in job["dlayers"]], tuple(job["ddims"]), self.maxB)
+        for dn in (self.dnG, self.dnD):
+            assert dn.ws.numel() * 4 - lib.fg_net_workspace_bytes(dn.h, self.maxB) in (0, 1, 2, 3)
+        self.gan = FusedGan(ctx, self.dnG, self.dnD, self.table, self.maxB)
+        self.gan.set_seeds(3, 0, 777, 0)
+        cfg = job.get("cfg")
+        if cfg:
+            p = cfg["pen"]
+            self.gan.set_penalty(0, p["D_L1"], p["D_L2"], p["D_clamp"]); self.gan.set_penalty(1, p["G_L1"], p["G_L2"], p["G_clamp"])
+            self.gan.set_optimizer(0, *cfg["optD"]); self.gan.set_optimizer(1, *cfg["optG"])
+            if cfg["bucket"]:
+                ctx.check(lib.fg_test_set_gan_bucket_target(self.gan.h, cfg["bucket"]))
+        self.gan._bind()
+        c, h, w = job["ddims"]
+        self.img, self.nz = c * h * w, (h * w if self.table else job["gdims"][0])
+        E = torch.zeros
+        self.real, self.cond, self.noise = E(self.maxB * self.img), E(self.maxB * self.img), E(self.maxB * self.nz)
+        self.masks = [torch.ones(max(1, lib.fg_net_mask_elems(self.dnD.h, i, self.maxB))) for i in range(self.dnD.n_masks)]
+        self.mp = (ctypes.c_void_p * max(1, len(self.masks)))(*[m.data_ptr() for m in self.masks])
+    def call(self, which, B, explicit, flags=0, real=True):
+        P = lambda t, on=True: t.data_ptr() if on else None
+        nz, mp = P(self.noise, explicit), (self.mp if explicit and self.masks else None)
+        if which == "D":
+            return lib.fg_step_D(self.gan.h, B, P(self.real, real), P(self.cond, self.table), P(self.cond, self.table), nz, mp, flags)
+        return lib.fg_step_G(self.gan.h, B, P(self.cond, self.table), nz, mp, flags)
+    def offsets(self):
+        a, b = ctypes.c_longlong(), ctypes.c_longlong()
+        ctx.check(lib.fg_gan_get_offsets(self.gan.h, ctypes.byref(a), ctypes.byref(b)))
+        return [a.value, b.value]
+    def d_output_count(self):
+        o, c = ctypes.c_longlong(), ctypes.c_longlong()
+        ctx.check(lib.fg_gan_buffer(self.gan.h, 7, ctypes.byref(o), ctypes.byref(c)))
+        return c.value
+
+def run_pair(job, grids=False):
+    settings(dict(math=0, fusion=%(default)d))
+    res = dict(job, rc={}, log={})
+    launches()
+    def done(p, rc, msg=None):
+        res["rc"][p] = [rc, (lib.fg_last_error(ctx.h).decode() if msg is None else msg) if rc else ""]
+        res["log"].setdefault(p, []).extend(launches())
+        return rc
+    def finish():
+        os.ftruncate(LOG.fileno(), 0); RD.seek(0)
+        if not grids:
+            res["log"] = {p: sorted(set(" ".join(l.split(" grid=")[0:1] + l.split(" ")[-2:]) for l in v)) for p, v in res["log"].items()}
+        print(json.dumps(res), flush=True)
+    try:
+        pr = Pair(job)
+    except FgError as e:
+        m = re.match(r"libfacegen_hip error (-?\d+): (.*)", str(e), re.S)
+        done("create", int(m.group(1)) if m else -99, m.group(2) if m else str(e))
+        return finish()
+    done("create", 0)
+    for B in job["batches"]:
+        for explicit in (False, True):
+            tag = "@%%d%%s" %% (B, "x" if explicit else "n")
+            done("D" + tag, pr.call("D", B, explicit))
+            done("G" + tag, pr.call("G", B, explicit))
+            if not done("Dn" + tag, pr.call("D", B, explicit, 1)):
+                done("uD" + tag, lib.fg_gan_update(pr.gan.h, 0))
+            if not done("Gn" + tag, pr.call("G", B, explicit, 1)):
+                done("uG" + tag, lib.fg_gan_update(pr.gan.h, 1))
+    if job.get("scenarios"):
+        scenarios(job, res, done)
+    finish()
+
+def scenarios(job, res, done):
+    M = job["max_batch"]
+    extra = res.setdefault("extra", {})
+    # (c) a refused step leaves the offsets of the random streams alone: the same calls on a pair that is refused in between and on a
+    # fresh twin with the same seeds
+    def drawn(refusals):
+        pr = Pair(job)
+        out = [pr.offsets()]
+        assert pr.call("D", M, False) == 0 and pr.call("G", M, False) == 0
+        out.append(pr.offsets())
+        codes = refusals(pr) if refusals else {}
+        out.append(pr.offsets())
+        assert pr.call("D", M, False) == 0
+        out.append(pr.offsets())
+        assert pr.call("G", 2, False) == 0
+        out.append(pr.offsets())
+        return out, codes
+    def refusals(pr):
+        g, codes = pr.gan, {}
+        codes["fg_step_D at an odd batch"] = pr.call("D", M - 1, False)
+        codes["fg_step_G at an odd batch"] = pr.call("G", M - 1, False)
+        codes["fg_step_D above max_batch"] = pr.call("D", M + 2, False)
+        codes["fg_step_G above max_batch"] = pr.call("G", M + 2, False)
+        codes["fg_step_D with a null real"] = pr.call("D", M, False, real=False)
+        key = pr.gan._bound
+        ctx.check(lib.fg_gan_bind_workspaces(g.h, key[0], key[1] * 4, key[2], 16))
+        codes["FG_ERR_WORKSPACE: fg_step_D with D's workspace bound too small"] = pr.call("D", M, False)
+        codes["FG_ERR_WORKSPACE: fg_step_G with D's workspace bound too small"] = pr.call("G", M, False)
+        ctx.check(lib.fg_gan_bind_workspaces(g.h, key[0], 16, key[2], key[3] * 4))
+        codes["FG_ERR_WORKSPACE: fg_step_D with G's workspace bound too small"] = pr.call("D", M, False)
+        codes["FG_ERR_WORKSPACE: fg_step_G with G's workspace bound too small"] = pr.call("G", M, False)
+        ctx.check(lib.fg_gan_bind_workspaces(g.h, key[0], key[1] * 4, key[2], key[3] * 4))
+        return codes
+    used, codes = drawn(refusals)
+    twin, _ = drawn(None)
+    extra["offsets"] = dict(used=used, twin=twin, codes=codes)
+    # (d) FG_GAN_D_OUTPUT reports the batch of the last closure
+    if M >= 4:
+        pr = Pair(job)
+        assert pr.call("D", M, True) == 0 and pr.call("G", M - 2, True) == 0
+        a = pr.d_output_count()
+        assert pr.call("D", M, True) == 0
+        extra["d_output"] = dict(M=M, after_D_then_G=a, after_G_then_D=pr.d_output_count())
+    launches()
+    # item 4: the bucketed generator backward on a transport-less communicator
+    pr0 = Pair(job)
+    ns = lib.fg_net_num_stages(pr0.dnG.h)
+    if ns >= 3:
+        from face_generator_amd.distributed import DryCollective
+        nP = lib.fg_net_num_params(pr0.dnG.h)
+        stages = []
+        for s in range(ns):
+            lo, hi = ctypes.c_longlong(), ctypes.c_longlong()
+            ctx.check(lib.fg_net_stage_params(pr0.dnG.h, s, ctypes.byref(lo), ctypes.byref(hi)))
+            stages.append([lo.value, hi.value])
+        runs = []
+        for world in (2, 4):
+            for target in (1, max(2, nP // 3), nP):
+                pr = Pair(job)
+                coll = DryCollective(ctx, 0, world)
+                pr.gan.set_comm(coll, sync_bn=False, overlap=1)
+                ctx.check(lib.fg_test_set_gan_bucket_target(pr.gan.h, target))
+                assert pr.call("D", M, True) == 0
+                ctx.check(lib.fg_gan_finish_pending(pr.gan.h))
+                coll.schedule(reset=True)
+                launches()
+                assert pr.call("G", M, True) == 0
+                runs.append(dict(world=world, target=target, schedule=coll.schedule(reset=True), log=launches()))
+                pr.gan.set_comm(None)
+        extra["buckets"] = dict(nP=nP, stages=stages, runs=runs)
+"""
+
+GAN_SWEEP = GAN_ENGINE + r"""
+guarded(lambda: [run_pair(j) for j in json.load(open(sys.argv[1]))])
+"""
+
+GAN_REPLAY = GAN_ENGINE + r"""
+def replay_all():
+    for c in GC.GAN_CASES:
+        run_pair(dict(list="GAN_CASES", kind="gan", case=c.name, gdims=list(c.gdims), glayers=[list(l) for l in c.glayers], ddims=list(c.ddims),
+                      dlayers=[list(l) for l in c.dlayers], table=c.table, max_batch=c.max_batch, batches=GC.SWEEP_BATCHES(c.max_batch), shape=[], math=0,
+                      fusion=%(default)d, cfg=dict(optD=list(c.optD), optG=list(c.optG), pen=c.pen, bucket=c.bucket), scenarios=True), grids=True)
+    for (name, row, gd, gl, dd, dl, table, mb, msg) in GC.REFUSED_GAN_CASES:
+        run_pair(dict(list="REFUSED_GAN_CASES", kind="gan", case=name, gdims=list(gd), glayers=[list(l) for l in gl], ddims=list(dd),
+                      dlayers=[list(l) for l in dl], table=table, max_batch=mb, batches=[2], shape=[], math=0, fusion=%(default)d))
+guarded(replay_all)
+"""
+
+
+@memo
+def gan_replay():
+    """GAN_CASES and REFUSED_GAN_CASES of tests/gan_cases.py under each case's own optimizers and penalties -> parsed jobs (full launch
+    lines per pass; "extra": the scenarios of tests/test_gan_steps_host.py)"""
+    p = _run_stdout(GAN_REPLAY)
+    out, err = p.communicate(timeout=600)
+    assert p.returncode == 0, err[-3000:]
+    return _parse_net_jobs(out.splitlines())
+
+
+@memo
+def gan_sweep():
+    """every generated pair at every even batch of {2, 4, 6, max_batch - 2, max_batch} -> parsed jobs (unique signatures per pass)"""
+    import tempfile
+    import gan_cases as GC
+    jobs = [dict(list="gan-sweep", kind="gan", idx=i, gdims=list(gd), glayers=[list(l) for l in gl], ddims=list(dd), dlayers=[list(l) for l in dl], table=t,
+                 max_batch=mb, batches=GC.SWEEP_BATCHES(mb), shape=[], math=0, fusion=FG_FUSE_DEFAULT)
+            for i, (gd, gl, dd, dl, t, mb) in enumerate(GC.random_pairs(GC.SWEEP_SEED, GC.SWEEP_N))]
+    workers = max(1, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4))
+    files, procs = [], []
+    try:
+        for k in range(workers):
+            f = tempfile.NamedTemporaryFile("w", suffix=".json", delete=False)
+            json.dump(jobs[k::workers], f); f.close()
+            o = tempfile.NamedTemporaryFile("w+", suffix=".out", delete=False)
+            files += [f.name, o.name]
+            procs.append((_run_stdout(GAN_SWEEP, [f.name], out=o), o))
+        res = []
+        for p, o in procs:
+            _, err = p.communicate(timeout=900)
+            assert p.returncode == 0, err[-3000:]
+            o.seek(0)
+            res += _parse_net_jobs(o.read().splitlines())
+            o.close()
+    finally:
+        for f in files:
+            os.unlink(f)
+    return sorted(res, key=lambda j: j["idx"])
 
 
 def _parse_net_jobs(lines):

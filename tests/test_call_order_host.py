@@ -150,7 +150,7 @@ def test_optimizer_moves_reach_the_fused_and_the_unfused_update(run, pair):
 
 def test_return_codes(run):
     rc = run[("return_codes", "-")]["rc"]
-    assert len(rc) >= 29
+    assert len(rc) >= 36
     bad = []
     for name, code in rc.items():
         want = (0 if name.startswith("FG_OK:") else CO.FG_ERR_WORKSPACE if name.startswith("FG_ERR_WORKSPACE:")

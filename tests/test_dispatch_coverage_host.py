@@ -41,7 +41,7 @@ def audit():
     t0 = time.time()
     out = dict(replay=A.replay(), sweep=A.sweep(), nets=A.net_launches(),
                strided_replay=A.strided_replay(), strided_sweep=A.strided_sweep(extra=STRIDED_REFUSED), pointwise=A.pointwise_replay(),
-               net_replay=A.net_replay())
+               net_replay=A.net_replay(), gan_replay=A.gan_replay())
     out["seconds"] = time.time() - t0
     return out
 
@@ -272,7 +272,8 @@ def test_every_launch_site_is_entered_in_the_ledger_with_one_status(audit):
     assert all(st in STATUSES for st, _ in rows.values()), {k: v for k, v in rows.items() if v[0] not in STATUSES}
     # replay: the conv / linear lists, STRIDED_CASES, and the module-level lists of tests/test_gpu_pointwise_paths.py
     # ... and NET_CASES of tests/net_cases.py (whole nets, each compared with the float64 oracle by tests/test_gpu_net_fusions.py)
-    repk = {A.kernel_of(s[0]) for k in ("replay", "strided_replay", "pointwise", "net_replay") for s in A.all_sigs(audit[k])}
+    # ... and GAN_CASES of tests/gan_cases.py (G / D pairs at the step level, each compared with it by tests/test_gpu_gan_steps.py)
+    repk = {A.kernel_of(s[0]) for k in ("replay", "strided_replay", "pointwise", "net_replay", "gan_replay") for s in A.all_sigs(audit[k])}
     swk = {A.kernel_of(s[0]) for k in ("sweep", "strided_sweep") for s in A.all_sigs(audit[k])}
     netk = {A.kernel_of(A.sig_of(l)[0]) for v in audit["nets"].values() for l in v}
     meas = measure_only_sites()

@@ -19,7 +19,7 @@ DOC = os.path.join(A.ROOT, "tests", "NET_FUSIONS.md")
 NOW_OPERATOR = ["actmaxpool_fwd_kernel", "colsum_final_thin_kernel", "colsum_perm_kernel", "gemv_bwd_act_kernel", "igemm_act_kernel",
                 "maxpool_prelu_bwd_kernel", "sum_splits_actbwd_kernel", "thin_in_mfma_pad_kernel", "thin_out_rows_gather_kernel",
                 "thin_out_rows_mfma_kernel"]
-STEP_LEVEL = ["bce_kernel", "rng_multi_kernel", "add_halves_kernel", "copy_kernel"]     # fg_step_* / fg_gan_*: out of a net's reach
+STEP_LEVEL = ["bce_kernel", "rng_multi_kernel", "add_halves_kernel", "copy_kernel"]     # fg_step_* / fg_gan_*: out of a net's reach (tests/gan_cases.py)
 TOO_LARGE = ["igemm_ws_act_kernel"]     # smallest net that reaches it: 8.4 M output activations (NET_FUSIONS.md, "Known limits")
 
 
@@ -124,7 +124,8 @@ def test_every_case_launches_the_kernels_it_names(audit):
 
 
 def test_the_ledger_rows_of_the_kernels_only_nets_reached(audit):
-    """(d) each of them is launched by a NET_CASES entry the ledger names; the step-level ones stay `net-only`"""
+    """(d) each of them is launched by a NET_CASES entry the ledger names; the step-level ones are out of a net's reach: no NET_CASES
+    entry launches them, their rows are `operator` through GAN_CASES (tests/test_gan_steps_host.py holds those rows)"""
     rows = A.ledger_rows()
     by_kernel = {}
     for j in audit["replay"]:
@@ -135,7 +136,9 @@ def test_the_ledger_rows_of_the_kernels_only_nets_reached(audit):
         st, note = rows[k]
         named = set(re.findall(r"`((?:r\d+|s)-[\w-]+)`", note))
         assert st == "operator" and named and named <= by_kernel.get(k, set()), "%s: %s %s; launched by %s" % (k, st, sorted(named), sorted(by_kernel.get(k, ()))[:4])
-    for k in STEP_LEVEL + TOO_LARGE:
+    for k in STEP_LEVEL:
+        assert rows[k][0] == "operator" and "`GAN_CASES`" in rows[k][1] and k not in by_kernel, k
+    for k in TOO_LARGE:
         assert rows[k][0] == "net-only" and k not in by_kernel, k
     # the 4096-block cap of actmaxpool_fwd_kernel: one quad per thread, so more than 4096 x 256 quads of the POOLED tensor, that is
     # an input of more than 16 777 216 floats (64 MiB) -- above the 64 MB the GPU module allows a case: the row stays "none"
