@@ -1,5 +1,6 @@
 // Step-level entries of libfacegen_hip.so: the exchange step of data parallelism behind the C ABI (fg_comm_* : RCCL over
-// xGMI, bound at run time), and the evaluation reduction of adversarial.approxParzen.
+// xGMI, bound at run time), the evaluation reduction of adversarial.approxParzen and its many-query form, the nearest-neighbour
+// search of sample.lua's findClosestNeighboursOf (fg_nearest_update).
 #include "fg_internal.h"
 #include "../../include/facegen_hip.h"
 #include <dlfcn.h>
@@ -14,28 +15,165 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-// one block per generation i: dist[i] = || (gen[i] + cond) - fine ||_2, squares accumulated in fp64 like THTensor_(dist)
-__global__ __launch_bounds__(256) void parzen_dist_kernel(const float* __restrict__ gen, const float* __restrict__ cond,
-                                                          const float* __restrict__ fine, long long elems,
-                                                          float* __restrict__ dist) {
-    __shared__ double sh[4];
-    const float* g = gen + (long long)blockIdx.x * elems;
-    double acc = 0.0;
-    for (long long e = threadIdx.x; e < elems; e += 256) {
-        const float v = g[e] + cond[e];          // neighbors:add(condInputs) rounds to fp32 first (:322)
-        const float d = v - fine[e];
-        acc += (double)d * (double)d;
+// Nearest-neighbour search (sample.lua:133-151, findClosestNeighboursOf) is the same reduction with many queries per pass over
+// the rows, so both live in one template.  COND = true is approxParzen's instance: one block of 256 per generation i,
+// dist[i] = || (rows[i] + cond) - queries ||_2 for ONE query, squares accumulated in fp64 like THTensor_(dist).
+// COND = false streams the rows once for a group of qn <= QG queries and writes d2[j][i] = sum_e ((double)(rows[i][e] - queries[j][e]))^2:
+//   - a block of 8 waves takes NN_ROWS = 16 consecutive rows, two per wave;
+//   - the queries pass through LDS in slices of NN_CH elements (16 queries of 3072 floats do not fit whole);
+//   - lane l of a row's wave owns elements 4l .. 4l + 3 of every 256, adds their squares in ascending order into one fp64
+//     accumulator per (row, query), and the 64 partials are summed by the xor tree 32, 16, .. 1.
+// That order depends on elems alone -- not on the row's place in the call, on n, qn, QG or VEC (VEC only picks 16-byte or 4-byte
+// loads of the same elements) -- so equal rows give bit-equal sums however the set is cut into calls.
+#define NN_CH 512
+#define NN_ROWS 16
+template <bool VEC>
+__device__ __forceinline__ float4 nn_load4(const float* __restrict__ p, long long e, long long elems) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);          // past the end: 0 - 0 adds nothing to any sum
+    if constexpr (VEC) {
+        if (e < elems) v = *reinterpret_cast<const float4*>(p + e);
+    } else {
+        if (e < elems) v.x = p[e];
+        if (e + 1 < elems) v.y = p[e + 1];
+        if (e + 2 < elems) v.z = p[e + 2];
+        if (e + 3 < elems) v.w = p[e + 3];
     }
-    acc = wave_sum_f64(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) dist[blockIdx.x] = (float)sqrt(sh[0] + sh[1] + sh[2] + sh[3]);
+    return v;
 }
-__global__ __launch_bounds__(64) void min_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
-    float m = 1e10f;                             // `local dist = 1e10` (:324)
-    for (int i = threadIdx.x; i < n; i += 64) m = fminf(m, v[i]);
-    for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o, 64));
-    if (threadIdx.x == 0) out[0] = m;
+__device__ __forceinline__ double nn_acc4(double acc, const float4 r, const float4 q) {
+    const float d0 = r.x - q.x, d1 = r.y - q.y, d2 = r.z - q.z, d3 = r.w - q.w;     // the difference rounds to fp32 first
+    acc += (double)d0 * (double)d0;
+    acc += (double)d1 * (double)d1;
+    acc += (double)d2 * (double)d2;
+    acc += (double)d3 * (double)d3;
+    return acc;
+}
+// sums M values per lane over the wave with the pairing of wave_sum_f64, each value in one lane only: while more than one value is
+// left, a lane keeps one half and hands the other to its partner.  Value v ends in the lanes l with l >> (6 - log2 M) == v.
+template <int M, int OFF>
+__device__ __forceinline__ void nn_wave_fold(double* a, int lane) {
+    if constexpr (OFF > 0) {
+        if constexpr (M > 1) {
+            constexpr int H = M / 2;
+            const bool up = (lane & OFF) != 0;
+#pragma unroll
+            for (int i = 0; i < H; ++i) {
+                const double keep = up ? a[i + H] : a[i], send = up ? a[i] : a[i + H];
+                a[i] = keep + __shfl_xor(send, OFF, 64);
+            }
+            nn_wave_fold<H, OFF / 2>(a, lane);
+        } else {
+            a[0] += __shfl_xor(a[0], OFF, 64);
+            nn_wave_fold<1, OFF / 2>(a, lane);
+        }
+    }
+}
+template <int QG, bool COND, bool VEC>
+__global__ __launch_bounds__(COND ? 256 : 512) void parzen_dist_kernel(const float* __restrict__ rows, const float* __restrict__ cond,
+                                                                       const float* __restrict__ queries, long long elems, int n, int qn,
+                                                                       float* __restrict__ dist, double* __restrict__ d2) {
+    if constexpr (COND) {
+        __shared__ double sh[4];
+        const float* g = rows + (long long)blockIdx.x * elems;
+        double acc = 0.0;
+        for (long long e = threadIdx.x; e < elems; e += 256) {
+            const float v = g[e] + cond[e];          // neighbors:add(condInputs) rounds to fp32 first (:322)
+            const float d = v - queries[e];
+            acc += (double)d * (double)d;
+        }
+        acc = wave_sum_f64(acc);
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) dist[blockIdx.x] = (float)sqrt(sh[0] + sh[1] + sh[2] + sh[3]);
+    } else {
+        constexpr int S = NN_CH / 256;                   // float4 per lane and row in one slice
+        __shared__ float4 sq[QG * (NN_CH / 4)];
+        const int lane = threadIdx.x & 63;
+        const long long r0 = (long long)blockIdx.x * NN_ROWS + (threadIdx.x >> 6) * 2;
+        // a row past the end reads row n - 1 again and stores nothing
+        const float* __restrict__ pa = rows + (r0 < n ? r0 : n - 1) * elems;
+        const float* __restrict__ pb = rows + (r0 + 1 < n ? r0 + 1 : n - 1) * elems;
+        double acc[2 * QG];
+#pragma unroll
+        for (int i = 0; i < 2 * QG; ++i) acc[i] = 0.0;
+        float4 ra[S], rb[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            ra[s] = nn_load4<VEC>(pa, s * 256 + lane * 4, elems);
+            rb[s] = nn_load4<VEC>(pb, s * 256 + lane * 4, elems);
+        }
+        for (long long e0 = 0; e0 < elems; e0 += NN_CH) {
+            __syncthreads();                             // the slice before this one has been read
+            for (int i = threadIdx.x; i < QG * (NN_CH / 4); i += 512) {
+                const int j = i / (NN_CH / 4);
+                sq[i] = j < qn ? nn_load4<VEC>(queries + (long long)j * elems, e0 + (i % (NN_CH / 4)) * 4, elems)
+                               : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            __syncthreads();
+            float4 na[S], nb[S];                         // the rows' next slice is under way while this one is summed
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                na[s] = nn_load4<VEC>(pa, e0 + NN_CH + s * 256 + lane * 4, elems);
+                nb[s] = nn_load4<VEC>(pb, e0 + NN_CH + s * 256 + lane * 4, elems);
+            }
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+#pragma unroll
+                for (int j = 0; j < QG; ++j) {
+                    const float4 qv = sq[j * (NN_CH / 4) + s * 64 + lane];
+                    acc[j] = nn_acc4(acc[j], ra[s], qv);
+                    acc[QG + j] = nn_acc4(acc[QG + j], rb[s], qv);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < S; ++s) { ra[s] = na[s]; rb[s] = nb[s]; }
+        }
+        nn_wave_fold<2 * QG, 32>(acc, lane);
+        constexpr int SPREAD = 64 / (2 * QG);            // lanes that hold one value
+        const int v = lane / SPREAD, j = v % QG;
+        const long long r = r0 + v / QG;
+        if (lane % SPREAD == 0 && r < n && j < qn) d2[(long long)j * n + r] = acc[0];
+    }
+}
+// ARG = false: approxParzen's minimum over the n distances of one example.  ARG = true: one block of 256 per query folds
+// v[j][0 .. n) into the running (out[j], out_index[j]) with the rule of sample.lua:142 -- a row wins only with a strictly smaller
+// d2, so the lowest index wins among equals and a NaN never wins -- and writes out_dist[j] = sqrt(out[j]).
+template <bool ARG, typename T>
+__global__ __launch_bounds__(ARG ? 256 : 64) void min_kernel(const T* __restrict__ v, int n, T* __restrict__ out, long long first_index,
+                                                             int first, int* __restrict__ out_index, float* __restrict__ out_dist) {
+    if constexpr (!ARG) {
+        float m = 1e10f;                             // `local dist = 1e10` (:324)
+        for (int i = threadIdx.x; i < n; i += 64) m = fminf(m, v[i]);
+        for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o, 64));
+        if (threadIdx.x == 0) out[0] = m;
+    } else {
+        __shared__ double sm[4];
+        __shared__ int si[4];
+        const T* __restrict__ row = v + (long long)blockIdx.x * n;
+        double m = INFINITY;
+        int at = n;                                  // "none": above every row of the call
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const double d = row[i];
+            if (d < m) { m = d; at = i; }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const double om = __shfl_xor(m, o, 64);
+            const int oa = __shfl_xor(at, o, 64);
+            if (om < m || (om == m && oa < at)) { m = om; at = oa; }
+        }
+        if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = m; si[threadIdx.x >> 6] = at; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < 4; ++w)
+                if (sm[w] < m || (sm[w] == m && si[w] < at)) { m = sm[w]; at = si[w]; }
+            double best = first ? (double)INFINITY : out[blockIdx.x];
+            int best_at = first ? -1 : out_index[blockIdx.x];
+            if (m < best) { best = m; best_at = (int)(first_index + at); }      // every carried row has a lower index
+            out[blockIdx.x] = best;
+            out_index[blockIdx.x] = best_at;
+            out_dist[blockIdx.x] = (float)sqrt(best);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -111,12 +249,54 @@ int fg_parzen_min_dist(fg_ctx* ctx, const float* gen, const float* cond, const f
                        float* dist, float* min_out) {
     if (!ctx || !gen || !cond || !fine || !dist || n <= 0 || elems <= 0)
         return fg_set_err(ctx, FG_ERR_INVALID, "fg_parzen_min_dist: bad argument");
-    hipLaunchKernelGGL(parzen_dist_kernel, dim3(n), dim3(256), 0, ctx->stream, gen, cond, fine, elems, dist);
+    hipLaunchKernelGGL((parzen_dist_kernel<1, true, false>), dim3(n), dim3(256), 0, ctx->stream, gen, cond, fine, elems, n, 1, dist,
+                       (double*)nullptr);
     FG_CHECK_LAUNCH(ctx);
     if (min_out) {
-        hipLaunchKernelGGL(min_kernel, dim3(1), dim3(64), 0, ctx->stream, (const float*)dist, n, min_out);
+        hipLaunchKernelGGL((min_kernel<false, float>), dim3(1), dim3(64), 0, ctx->stream, (const float*)dist, n, min_out, 0LL, 0,
+                           (int*)nullptr, (float*)nullptr);
         FG_CHECK_LAUNCH(ctx);
     }
+    return FG_OK;
+}
+
+size_t fg_nearest_workspace_bytes(int q, int n) {
+    return q > 0 && n > 0 ? (size_t)q * (size_t)n * sizeof(double) : 0;      // d2[q][n]
+}
+
+int fg_nearest_update(fg_ctx* ctx, const float* queries, int q, const float* rows, int n, long long elems, long long first_index,
+                      int first, double* best_d2, int* best_index, float* best_dist, void* scratch, size_t scratch_bytes) {
+    if (!ctx || !queries || !rows || !best_d2 || !best_index || !best_dist || !scratch)
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_nearest_update: NULL argument");
+    if (q <= 0 || n <= 0 || elems <= 0)
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_nearest_update: q = %d, n = %d, elems = %lld must all be positive", q, n, elems);
+    if (n > 1048576)
+        return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "fg_nearest_update: n = %d rows in one call (at most 1048576: feed the set in chunks)", n);
+    if (first_index < 0 || first_index + n > 2147483647LL)
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_nearest_update: rows %lld .. %lld do not fit a 31-bit index", first_index,
+                          first_index + n - 1);
+    if ((uintptr_t)scratch % sizeof(double))
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_nearest_update: scratch must be 8-byte aligned");
+    if (scratch_bytes < fg_nearest_workspace_bytes(q, n))
+        return fg_set_err(ctx, FG_ERR_WORKSPACE, "fg_nearest_update: scratch of %zu bytes, %zu needed for q = %d, n = %d", scratch_bytes,
+                          fg_nearest_workspace_bytes(q, n), q, n);
+    double* d2 = (double*)scratch;
+    const bool vec = elems % 4 == 0 && ((uintptr_t)queries | (uintptr_t)rows) % 16 == 0;
+#define NN_LAUNCH(QG, VEC)                                                                                                     \
+    hipLaunchKernelGGL((parzen_dist_kernel<QG, false, VEC>), dim3(fg_cdiv(n, NN_ROWS)), dim3(512), 0, ctx->stream, rows,         \
+                       (const float*)nullptr, queries + (long long)j0 * elems, elems, n, qn, (float*)nullptr, d2 + (long long)j0 * n)
+    for (int j0 = 0; j0 < q;) {                          // groups of 16 queries; the rest in the smallest instance that holds it
+        const int left = q - j0, qg = left > 4 ? 16 : left > 1 ? 4 : 1, qn = left < qg ? left : qg;
+        if (qg == 16) { if (vec) NN_LAUNCH(16, true); else NN_LAUNCH(16, false); }
+        else if (qg == 4) { if (vec) NN_LAUNCH(4, true); else NN_LAUNCH(4, false); }
+        else { if (vec) NN_LAUNCH(1, true); else NN_LAUNCH(1, false); }
+        FG_CHECK_LAUNCH(ctx);
+        j0 += qn;
+    }
+#undef NN_LAUNCH
+    hipLaunchKernelGGL((min_kernel<true, double>), dim3(q), dim3(256), 0, ctx->stream, (const double*)d2, n, best_d2, first_index, first,
+                       best_index, best_dist);
+    FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }
 

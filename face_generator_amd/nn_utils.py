@@ -99,6 +99,33 @@ def sortImagesByPrediction(images, ascending=False, nbMaxOut=None):
     return [imgs[i] for i in order.tolist()], [float(preds[i]) for i in order.tolist()]
 
 
+def _set_rows(trainingSet, lo, hi):
+    """rows lo .. hi - 1 of a training set as one host float32 [n][C][H][W] tensor."""
+    if callable(getattr(trainingSet, "size", None)) and not torch.is_tensor(trainingSet):
+        return torch.stack([torch.as_tensor(trainingSet[i], dtype=torch.float32) for i in range(lo, hi)])
+    return torch.as_tensor(trainingSet[lo:hi], dtype=torch.float32)
+
+
+def findClosestNeighboursOf(images, trainingSet, chunk_rows=8192, ctx=None):
+    """sample.lua:133-151 on the device (runtime.NearestSearch): the nearest training image (2-norm, torch.dist) of each image.
+    images: device NHWC [q][H][W][C]; they are converted to NCHW once, so that the set streams in the CHW order in which it is
+    stored.  trainingSet: a [N][C][H][W] float32 tensor or array, or any object with size() and [i] as dataset.lua returns.
+    -> ([(index, distance)] per image, the q neighbour images [q][C][H][W] gathered on the host by index).  The first of equally
+    near training images wins (the strict `<` of sample.lua:142)."""
+    from .runtime import NearestSearch
+    ctx = ctx or get_context()
+    N = trainingSet.size() if callable(getattr(trainingSet, "size", None)) and not torch.is_tensor(trainingSet) else len(trainingSet)
+    if N < 1:
+        raise ValueError("findClosestNeighboursOf: the training set is empty")
+    search = NearestSearch(ctx, ctx.to_nchw(images))
+    for lo in range(0, N, chunk_rows):
+        search.update(_set_rows(trainingSet, lo, min(lo + chunk_rows, N)), lo)
+    index, dist = search.result()
+    found = [(int(i), float(d)) for i, d in zip(index.tolist(), dist.tolist())]
+    neighbours = torch.stack([_set_rows(trainingSet, i, i + 1)[0] for i, _ in found])
+    return found, neighbours
+
+
 def switchToTrainingMode():
     """nn_utils.lua:207-213."""
     S.MODEL_G.training()

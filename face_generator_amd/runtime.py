@@ -680,3 +680,48 @@ class Sampler:
         self.ctx.check(self.lib.fg_image_grid(self.ctx.h, imgs.data_ptr(), self._p(order), int(k), c, h, w, int(nrow), int(padding),
                                               1 if normalize else 0, out.data_ptr(), None))
         return out
+
+
+class NearestSearch:
+    """findClosestNeighboursOf (sample.lua:133-151) as a streaming reduction on the device (fg_nearest_update): the nearest row of
+    a set to each of q queries, the set fed in chunks.  The object owns the scratch and the three running-result buffers; the
+    queries stay where the caller put them."""
+
+    def __init__(self, ctx, queries_dev):
+        """queries_dev: device float32 [q][elems] or [q][C][H][W], in the element order of the rows to come."""
+        self.ctx, self.lib = ctx, ctx.lib
+        if queries_dev.dtype != torch.float32 or queries_dev.dim() < 2:
+            raise FgError("NearestSearch: queries must be a float32 [q][elems] or [q][C][H][W] tensor")
+        self.queries = queries_dev.to(ctx.device).contiguous()
+        self.q = int(self.queries.shape[0])
+        self.elems = self.queries.numel() // max(self.q, 1)
+        new = torch.zeros if ctx.dry else torch.empty
+        self.best_d2 = new(self.q, dtype=torch.float64, device=ctx.device)
+        self.best_index = new(self.q, dtype=torch.int32, device=ctx.device)
+        self.best_dist = new(self.q, dtype=torch.float32, device=ctx.device)
+        self.scratch = None
+        self.fed = False
+
+    def update(self, rows, first_index):
+        """rows: device or host float32 [n][elems] / [n][C][H][W] carrying the indices first_index .. first_index + n - 1 (a host
+        chunk is uploaded here); at most 1048576 rows per call."""
+        rows = torch.as_tensor(rows)
+        if rows.dtype != torch.float32 or rows.dim() < 2 or rows.numel() != rows.shape[0] * self.elems:
+            raise FgError("NearestSearch.update: rows must be float32 [n][%d], got %s %s" % (self.elems, rows.dtype, tuple(rows.shape)))
+        rows = rows.to(self.ctx.device).contiguous()
+        n = int(rows.shape[0])
+        nbytes = self.lib.fg_nearest_workspace_bytes(self.q, n)
+        if self.scratch is None or self.scratch.numel() * 8 < nbytes:
+            self.scratch = (torch.zeros if self.ctx.dry else torch.empty)((nbytes + 7) // 8, dtype=torch.float64, device=self.ctx.device)
+        self.ctx.check(self.lib.fg_nearest_update(self.ctx.h, self.queries.data_ptr(), self.q, rows.data_ptr(), n, self.elems,
+                                                  int(first_index), 0 if self.fed else 1, self.best_d2.data_ptr(),
+                                                  self.best_index.data_ptr(), self.best_dist.data_ptr(), self.scratch.data_ptr(),
+                                                  self.scratch.numel() * 8))
+        self.fed = True
+
+    def result(self):
+        """-> (indices int32[q], dists float32[q]) on the host, with one copy back (-1 / +inf before the first row)."""
+        if not self.fed:
+            return torch.full((self.q,), -1, dtype=torch.int32), torch.full((self.q,), float("inf"))
+        both = torch.cat([self.best_index.view(torch.float32), self.best_dist]).cpu()
+        return both[:self.q].view(torch.int32).clone(), both[self.q:].clone()

@@ -2,12 +2,16 @@
 
 Per run: 1024 images from G, D's score for each, and five pictures -- 256 random ones, all 1024, the 64 best, the 64 worst and
 64 random ones -- under the file stems sample.lua:80-89 uses.  Noise, both nets, the rankings and the grids stay on the device;
-every finished grid is one device-to-host copy.  The nearest-neighbour search of `--neighbours` and the commented-out c2f chain
-are not part of this file.
+every finished grid is one device-to-host copy.  With `--neighbours --trainingSet PATH` a sixth picture follows
+(sample.lua:91-99): the 16 best samples, each above its nearest training image (nn_utils.findClosestNeighboursOf: the set streams
+through fg_nearest_update in chunks, the samples never leave the device).  PATH is a .npy of [N][C][H][W] float32 in [0, 1] or a
+directory of *.jpg / *.ppm / *.pgm files.  The commented-out c2f chain is not part of this file.
 
     python -m face_generator_amd.sample --save_base logs --writeto samples [--runs 1] [--batchSize 16] [--seed 1]
+                                        [--neighbours --trainingSet PATH]
 """
 import argparse
+import glob
 import os
 
 import torch
@@ -18,7 +22,9 @@ from .state import S
 
 N_IMAGES = 1024                      # sample.lua:80
 DEFAULTS = dict(save_base="logs", G_base="adversarial.net", D_base="adversarial.net", scale=32, grayscale=False,
-                writeto="samples", seed=1, gpu=0, runs=1, noiseDim=100, batchSize=16)
+                writeto="samples", seed=1, gpu=0, runs=1, noiseDim=100, batchSize=16, neighbours=False, trainingSet="")
+N_NEIGHBOURS = 16                    # sample.lua:94
+NEIGHBOURS_STEM = "best_%04d_neighbours_base"
 STEMS = ("random256_%04d_base", "random1024_%04d_base", "best_%04d_base", "worst_%04d_base", "random_%04d_base")
 
 
@@ -44,7 +50,8 @@ def picture_extension():
 def output_files(opt):
     """Every file main(opt) writes, in the order it writes them."""
     ext = picture_extension() or (".pgm" if opt.get("grayscale") else ".ppm")
-    return [os.path.join(opt["writeto"], stem % run + ext) for run in range(1, opt["runs"] + 1) for stem in STEMS]
+    stems = STEMS + ((NEIGHBOURS_STEM,) if opt.get("neighbours") else ())
+    return [os.path.join(opt["writeto"], stem % run + ext) for run in range(1, opt["runs"] + 1) for stem in stems]
 
 
 def save_picture(path, grid_chw):
@@ -78,6 +85,42 @@ def toGrid(sampler, order, k, nrow):
     return sampler.grid(order, k, nrow, padding=0, normalize=True).cpu()
 
 
+def loadTrainingSet(path, dims, ctx):
+    """--trainingSet -> host float32 [N][C][H][W] in [0, 1] at the sampled size.  A .npy holds exactly that.  A directory is read
+    as dataset.loadImages does (dataset.lua): its sorted *.jpg / *.ppm / *.pgm files, each scaled to dims with image.scale
+    (ops.scale_bilinear on the device)."""
+    import numpy as np
+    from . import ops
+    c, h, w = dims
+    if not os.path.isdir(path):
+        data = torch.from_numpy(np.load(path))
+        if data.dtype != torch.float32 or data.dim() != 4 or tuple(data.shape[1:]) != dims:
+            raise ValueError("--trainingSet %s: float32 [N][%d][%d][%d] expected, got %s %s" % (path, c, h, w, data.dtype, tuple(data.shape)))
+        return data
+    try:
+        import PIL.Image
+    except ImportError:
+        raise ValueError("--trainingSet %s: reading a directory of pictures needs PIL; pass a .npy instead" % path)
+    names = sorted(n for pat in ("*.jpg", "*.ppm", "*.pgm") for n in glob.glob(os.path.join(path, pat)))
+    if not names:
+        raise ValueError("--trainingSet %s: no *.jpg, *.ppm or *.pgm file" % path)
+    out = torch.empty((len(names), c, h, w))
+    for i, name in enumerate(names):
+        img = np.asarray(PIL.Image.open(name).convert("L" if c == 1 else "RGB"), dtype=np.float32) / 255.0
+        img = torch.from_numpy(img.reshape(img.shape[0], img.shape[1], c)).permute(2, 0, 1)[None]
+        out[i] = ops.scale_bilinear(img.to(ctx.device), w, h, "nchw", ctx).cpu()[0]
+    return out
+
+
+def toNeighboursGrid(sampler, best, neighbours_nhwc):
+    """sample.lua:156-168: sample 1, its neighbour, sample 2, ... as one picture of nrow = the number of samples, i.e. the samples
+    in the upper row and each one's neighbour below it.  One device buffer [samples ; neighbours] read in the order 0, k, 1, k + 1, ..."""
+    k = best.shape[0]
+    both = torch.cat([best, neighbours_nhwc])
+    order = torch.arange(2 * k, dtype=torch.int32).view(2, k).t().contiguous().view(-1).to(both.device)
+    return sampler.grid(order, 2 * k, k, padding=0, normalize=True, images=both).cpu()
+
+
 def loadModels(opt, dims):
     ck = nn_utils.load_checkpoint(os.path.join(opt["save_base"], opt["G_base"]), dims)
     G = _net_of(ck["G"], "G", dims, opt)
@@ -99,6 +142,8 @@ def main(opt=None, ctx=None):
     """-> the list of files written."""
     opt = dict(DEFAULTS, **(opt or {}))
     dims = (1 if opt["grayscale"] else 3, opt["scale"], opt["scale"])
+    if opt["neighbours"] and not opt["trainingSet"]:
+        raise ValueError("--neighbours needs the training set to search: pass --trainingSet PATH")
     ctx = ctx or get_context(opt["gpu"] if opt["gpu"] >= 0 else None)
     S.OPT.update(batchSize=opt["batchSize"], noiseDim=opt["noiseDim"], seed=opt["seed"], scale=opt["scale"],
                  grayscale=opt["grayscale"])
@@ -113,6 +158,8 @@ def main(opt=None, ctx=None):
     sm = Sampler(ctx, G._inner().device_net, D._inner().device_net, N_IMAGES, opt["batchSize"])
     sm.set_seed(opt["seed"], 0)
     files = output_files(opt)
+    per_run = len(STEMS) + (1 if opt["neighbours"] else 0)
+    trainingSet = loadTrainingSet(opt["trainingSet"], dims, ctx) if opt["neighbours"] else None
     print("Sampling...")
     for run in range(opt["runs"]):
         sm.sample(N_IMAGES)
@@ -122,7 +169,11 @@ def main(opt=None, ctx=None):
                  toGrid(sm, "ORDER_DESC", 64, 8),
                  toGrid(sm, "ORDER_ASC", 64, 8),
                  toGrid(sm, dev(selectRandomImagesFrom(N_IMAGES, 64, gen)), 64, 8)]
-        for path, grid in zip(files[run * len(STEMS):], grids):
+        if opt["neighbours"]:
+            best = sm.view("IMAGES").index_select(0, sm.view("ORDER_DESC")[:N_NEIGHBOURS].long())
+            _, neighbours = nn_utils.findClosestNeighboursOf(best, trainingSet, ctx=ctx)
+            grids.append(toNeighboursGrid(sm, best, ctx.to_device_nhwc(neighbours)))
+        for path, grid in zip(files[run * per_run:], grids):
             save_picture(path, grid)
             print("wrote %s" % path)
     print("Finished.")

@@ -490,6 +490,30 @@ int fg_sample(fg_sampler* s, int n, const float* noise);
 int fg_parzen_min_dist(fg_ctx* ctx, const float* gen, const float* cond, const float* fine, int n, long long elems,
                        float* dist, float* min_out);
 
+/* ---- findClosestNeighboursOf (sample.lua:133-151): the nearest training image of each of q queries, as one streaming reduction
+ *      over the training set.  The set is fed in chunks; the three result buffers are the state carried from chunk to chunk. ----
+ * queries [q][elems] and rows [n][elems]: contiguous device floats in the same element order.  The rows of one call carry the global
+ *   indices first_index .. first_index + n - 1.  best_d2 (device double[q]), best_index (device int[q]) and best_dist (device
+ *   float[q]) hold the running result; first != 0 ignores what they hold and starts from (+inf, -1).
+ * Distance: d2 = sum_e ((double)d_e)^2 with d_e = rows[i][e] - queries[j][e] rounded to fp32, the convention of THTensor_(dist)
+ *   that the approxParzen entry above states.  torch.dist is a dependency of the reference that is not vendored -- PARITY UNPINNED,
+ *   like the image grid entry.
+ * Order rule: a row replaces the running best only with d2 < best_d2[j] (the strict `<` of sample.lua:142): the earliest row wins
+ *   among equals, a later chunk never displaces an equal earlier one, and a NaN distance never wins.  After the call
+ *   best_dist[j] = (float)sqrt(best_d2[j]), +inf while best_index[j] == -1.
+ * Determinism: no atomics; the order in which the squares of one (query, row) pair are added depends on elems alone -- not on the
+ *   row's place in the call, on n, on q or on alignment -- so equal rows give bit-equal d2, and best_d2 / best_index are
+ *   bit-identical however the set is cut into calls.
+ * Limits: any q >= 1 (the entry walks groups of up to 16 queries; every group reads the rows once); 1 <= n <= 1048576 per call
+ *   (larger: FG_ERR_UNSUPPORTED, the message names n); first_index >= 0 and first_index + n <= 2^31 - 1; any elems >= 1.  Rows need
+ *   4-byte alignment only: 16-byte loads are used where elems % 4 == 0 and both bases are 16-byte aligned, 4-byte loads of the same
+ *   elements otherwise.  scratch (8-byte aligned) holds d2[q][n]: the workspace function's size; smaller is FG_ERR_WORKSPACE, and
+ *   nothing outside that size is touched.  NULL or non-positive arguments: FG_ERR_INVALID.  The entry stays on the context's stream
+ *   and never synchronises. */
+size_t fg_nearest_workspace_bytes(int q, int n);
+int fg_nearest_update(fg_ctx* ctx, const float* queries, int q, const float* rows, int n, long long elems, long long first_index,
+                      int first, double* best_d2, int* best_index, float* best_dist, void* scratch, size_t scratch_bytes);
+
 /* ---- the c2f data step in front of the train closure (dataset_c2f.lua:49-61, `dataset._toResult`) ----
  * fg_scale_bilinear = image.scale(src, width, height) of the Torch7 `image` package (default mode 'bilinear'; un-vendored luarocks
  * dependency, restated in oracle/image_scale.py): width pass then height pass; per axis up-scaling interpolates with

@@ -145,6 +145,8 @@ int fg_sample_generate(fg_sampler* s, int n, const float* noise);
 int fg_sample_score(fg_sampler* s, int n, const float* images);
 int fg_sample(fg_sampler* s, int n, const float* noise);
 int fg_parzen_min_dist(fg_ctx* ctx, const float* gen, const float* cond, const float* fine, int n, long long elems, float* dist, float* min_out);
+size_t fg_nearest_workspace_bytes(int q, int n);
+int fg_nearest_update(fg_ctx* ctx, const float* queries, int q, const float* rows, int n, long long elems, long long first_index, int first, double* best_d2, int* best_index, float* best_dist, void* scratch, size_t scratch_bytes);
 int fg_scale_bilinear(fg_ctx* ctx, const float* src, float* dst, int n, int c, int hs, int ws, int hd, int wd, int layout);
 int fg_c2f_coarse_diff(fg_ctx* ctx, const float* fine, float* coarse, float* diff, float* tmp, int n, int c, int s, int cs, int layout);
 size_t fg_conv2d_workspace_bytes(int batch, int h, int w, int cin, int cout, int k, int upsample2x);
@@ -736,8 +738,8 @@ function Sampler:order(which, k)              -- host table of the k best ('best
 end
 -- image.toDisplayTensor{input = images, nrow = nrow, padding = padding} over the first k entries of an order: 'best' / 'worst' (the
 -- sampler's rankings), a DeviceTensor holding k int32 indices (0-based), or nil for images 0 .. k-1.  -> host FloatTensor [C][GH][GW],
--- the one copy back per picture
-function Sampler:grid(order, k, nrow, padding, normalize)
+-- the one copy back per picture.  images: a DeviceTensor NHWC [*][H][W][C] to lay out instead of the sampler's own
+function Sampler:grid(order, k, nrow, padding, normalize, images)
     padding = padding or 0
     local optr = nil
     if order == 'best' then optr = ffi.cast('const int*', (self:ptr(C.FG_SAMPLER_ORDER_DESC)))
@@ -748,8 +750,8 @@ function Sampler:grid(order, k, nrow, padding, normalize)
     local ymaps = math.ceil(k / xmaps)
     local gh, gw = ymaps * (h + padding), xmaps * (w + padding)
     local dev = M.DeviceTensor(c * gh * gw)
-    local images = self:ptr(C.FG_SAMPLER_IMAGES)
-    check(C.fg_image_grid(ctx, images, optr, k, c, h, w, nrow, padding, (normalize == false) and 0 or 1, dev.ptr, nil))
+    local src = images and images.ptr or self:ptr(C.FG_SAMPLER_IMAGES)
+    check(C.fg_image_grid(ctx, src, optr, k, c, h, w, nrow, padding, (normalize == false) and 0 or 1, dev.ptr, nil))
     return dev:float():view(c, gh, gw)
 end
 -- k indices (host, 0-based numbers in a Lua table) -> DeviceTensor of int32 for Sampler:grid
@@ -760,6 +762,40 @@ function M.indexTensor(indices)
     local t = M.DeviceTensor(k)
     check(C.fg_h2d(ctx, t.ptr, host, k * 4))
     return t
+end
+
+-- (iv) findClosestNeighboursOf (sample.lua:133-151) as a streaming reduction: fg_nearest_update -------------------------------------
+-- queries: DeviceTensor [q][elems]; the set is fed in chunks of at most 1048576 rows in the same element order.  The object owns the
+-- scratch and the running result (best_d2 double[q] | best_index int[q] | best_dist float[q], 16 bytes per query in one allocation)
+local Nearest = {}
+Nearest.__index = Nearest
+function M.Nearest(queries, q, elems)
+    local state = M.DeviceTensor(4 * q)
+    local base = ffi.cast('char*', state.ptr)
+    return setmetatable({queries = queries, q = q, elems = elems, state = state, d2 = ffi.cast('double*', base),
+                         index = ffi.cast('int*', base + 8 * q), dist = ffi.cast('float*', base + 12 * q), fed = false}, Nearest)
+end
+-- rows: DeviceTensor [n][elems], or a host FloatTensor of that shape (uploaded here), carrying the 0-based indices
+-- firstIndex .. firstIndex + n - 1
+function Nearest:update(rows, n, firstIndex)
+    if torch.isTensor(rows) then rows = M.DeviceTensor(n * self.elems):copy(rows) end
+    local bytes = tonumber(C.fg_nearest_workspace_bytes(self.q, n))
+    if not self.scratch or self.scratch_bytes < bytes then
+        self.scratch, self.scratch_bytes = M.DeviceTensor(bytes / 4), bytes
+    end
+    check(C.fg_nearest_update(ctx, self.queries.ptr, self.q, rows.ptr, n, self.elems, firstIndex, self.fed and 0 or 1, self.d2,
+                              self.index, self.dist, self.scratch.ptr, self.scratch_bytes))
+    self.fed = true
+end
+-- -> host tables {index (0-based, -1 before the first row)}, {distance}: one copy back (synchronises)
+function Nearest:result()
+    local q = self.q
+    local host = ffi.new('int[?]', 2 * q)
+    check(C.fg_d2h(ctx, host, self.index, 8 * q))
+    local dist = ffi.cast('float*', host + q)
+    local indices, dists = {}, {}
+    for j = 1, q do indices[j], dists[j] = host[j - 1], dist[j - 1] end
+    return indices, dists
 end
 
 return M

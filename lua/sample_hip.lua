@@ -5,8 +5,10 @@ the same names: per run 1024 images, `random256_`, `random1024_`, `best_`, `wors
 What changes: the noise, G's and D's forward passes (chunks of OPT.batchSize, evaluate mode), the two rankings and the grids stay
 on the device -- one C call for sample.lua:80-85, one per grid, and one copy back per finished picture.  D scores every image once
 (the reference scores all of them again for "worst"; in evaluate mode that recomputes the same numbers).  Equal scores are
-ordered by index (table.sort leaves that open).  The `--neighbours` search and the commented-out c2f chain are not part of this
-file.
+ordered by index (table.sort leaves that open).  With OPT.neighbours a sixth picture follows (sample.lua:91-99,
+`best_%04d_neighbours_base.jpg`): the 16 best samples, each above its nearest training image.  The samples never leave the device;
+the training set streams through fg_nearest_update (FG.Nearest) in chunks, and the first of equally near images wins like the
+strict `<` of sample.lua:142.  The commented-out c2f chain is not part of this file.
 
 NOT EXECUTED IN THIS REPOSITORY'S ENVIRONMENT (no Lua / Torch7 in the image); face_generator_amd/sample.py is the executed mirror
 and tests/test_gpu_sampler.py checks the entries it calls.  Use from sample.lua once FG is bound (lua/patches/sample.lua.patch):
@@ -71,10 +73,43 @@ function sample.scoreRange(s, which, k)
     return preds[order[1] + 1], preds[order[#order] + 1]
 end
 
-local function save(stem, run, grid)
-    local filename = paths.concat(OPT.writeto, string.format('%s_%04d_base.jpg', stem, run))
+local function save(stem, run, grid, tail)
+    local filename = paths.concat(OPT.writeto, string.format('%s_%04d_%s.jpg', stem, run, tail or 'base'))
     image.save(filename, grid)
     return filename
+end
+
+-- sample.lua:91-99 + findClosestNeighboursOf + toNeighboursGrid: the k best samples and their nearest training images as one
+-- picture of nrow = k (sample 1, its neighbour, sample 2, ... in toDisplayTensor's order: the samples above, the neighbours below)
+sample.neighbours = 16
+sample.chunkRows = 8192
+function sample.neighboursGrid(s, k)
+    local c, h, w = s.dims[1], s.dims[2], s.dims[3]
+    local elems = c * h * w
+    -- [k samples ; k neighbours] NHWC: the samples by k device copies in the host order of the ranking
+    local both = FG.DeviceTensor(2 * k * elems)
+    local images = s:ptr(FG.C.FG_SAMPLER_IMAGES)
+    for i, idx in ipairs(s:order('best', k)) do
+        FG.check(FG.C.fg_d2d(FG.ctx, both.ptr + (i - 1) * elems, images + idx * elems, elems * 4))
+    end
+    -- the training set is stored CHW: convert the k queries once and stream the set as it is
+    local queries = FG.DeviceTensor(k * elems)
+    FG.check(FG.C.fg_nhwc_to_nchw(FG.ctx, both.ptr, queries.ptr, k, c, h, w))
+    local data = DATASET.loadImages(0, 9999999).data
+    local N = data:size(1)
+    local search = FG.Nearest(queries, k, elems)
+    for first = 0, N - 1, sample.chunkRows do
+        local n = math.min(sample.chunkRows, N - first)
+        search:update(data:narrow(1, first + 1, n), n, first)
+    end
+    local indices = search:result()
+    local found = torch.FloatTensor(k, c, h, w)
+    for i = 1, k do found[i] = data[indices[i] + 1] end
+    local nhwc = FG.to_device_nhwc(found)
+    FG.check(FG.C.fg_d2d(FG.ctx, both.ptr + k * elems, nhwc.ptr, k * elems * 4))
+    local order = {}
+    for i = 1, k do order[2 * i - 1], order[2 * i] = i - 1, k + i - 1 end
+    return s:grid(FG.indexTensor(order), 2 * k, k, 0, true, both)
 end
 
 function sample.main()
@@ -94,6 +129,9 @@ function sample.main()
         }
         for i, stem in ipairs(sample.stems) do
             written[#written + 1] = save(stem, run, grids[i])
+        end
+        if OPT.neighbours then
+            written[#written + 1] = save('best', run, sample.neighboursGrid(s, sample.neighbours), 'neighbours_base')
         end
         local b1, b2 = sample.scoreRange(s, 'best', 64)
         local w1, w2 = sample.scoreRange(s, 'worst', 64)
