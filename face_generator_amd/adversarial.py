@@ -17,6 +17,7 @@ import torch
 
 from . import interruptable_optimizers as IO
 from .nn import BCECriterion
+from .runtime import is_resident
 from .state import S
 
 
@@ -377,6 +378,7 @@ def train(dataset, maxAccuracyD=1.01, accsInterval=20):
             accs.pop(0)
         return mean(accs) < maxAccuracyD
     use_gate = maxAccuracyD <= 1.0
+    resident = is_resident(dataset)
 
     for t in range(1, N_epoch + 1, dataBatchSize):
         thisBatchSize = min(OPT["batchSize"], N_epoch - t + 1)
@@ -389,8 +391,11 @@ def train(dataset, maxAccuracyD=1.01, accsInterval=20):
         half = thisBatchSize // 2
         for _ in range(OPT.get("D_iterations", 1)):
             idx = [S.rng.randrange(dataset.size()) for _ in range(half)]            # math.random picks (:245)
-            real = torch.stack([torch.as_tensor(dataset[i], dtype=torch.float32) for i in idx])
-            real_d = ctx.to_device_nhwc(real)
+            if resident:                    # a set in HBM (runtime.DeviceDataset): dataset[i] for the batch is one gather there
+                real_d = dataset.gather(idx)
+            else:
+                real = torch.stack([torch.as_tensor(dataset[i], dtype=torch.float32) for i in idx])
+                real_d = ctx.to_device_nhwc(real)
             nz = None if tr.gan is not None else S.next_noise(ctx, half, OPT["noiseDim"])   # fused: drawn inside the step
             r = tr.step_D(real_d, nz, gate=gate if use_gate else None)
             pending.append(r["confusion"].clone())

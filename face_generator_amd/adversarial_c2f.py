@@ -6,6 +6,7 @@ import time
 import torch
 
 from .adversarial import Trainer
+from .runtime import is_resident
 from .state import S
 
 
@@ -97,10 +98,16 @@ def train(trainData):
     pending = []
     print("<trainer> Epoch #%d [batchSize = %d]" % (S.EPOCH, OPT["batchSize"]))
 
+    resident = is_resident(trainData)            # dataset_c2f.ResidentResult: the three sets live in HBM
+
+    def fetch(idx, field):
+        if resident:
+            return trainData.gather(idx, field)
+        return ctx.to_device_nhwc(torch.stack([torch.as_tensor(getattr(trainData[i], field), dtype=torch.float32) for i in idx]))
+
     def pick(n, field):
         idx = [S.rng.randrange(trainData.size()) for _ in range(n)]
-        return idx, ctx.to_device_nhwc(torch.stack([torch.as_tensor(getattr(trainData[i], field), dtype=torch.float32)
-                                                    for i in idx]))
+        return idx, fetch(idx, field)
     for t in range(1, N_epoch + 1, dataBatchSize):
         thisBatchSize = min(OPT["batchSize"], N_epoch - t + 1)
         if thisBatchSize < 4:
@@ -110,8 +117,12 @@ def train(trainData):
         half = thisBatchSize // 2
         for _ in range(OPT.get("D_iterations", 1)):
             idx = [S.rng.randrange(trainData.size()) for _ in range(half)]
-            diff = ctx.to_device_nhwc(torch.stack([torch.as_tensor(trainData[i].diff, dtype=torch.float32) for i in idx]))
-            cond_r = ctx.to_device_nhwc(torch.stack([torch.as_tensor(trainData[i].coarse, dtype=torch.float32) for i in idx]))
+            if resident:
+                idx = trainData.coarse.indices(idx)        # one upload serves both gathers
+                diff, cond_r = fetch(idx, "diff"), fetch(idx, "coarse")
+            else:
+                diff = ctx.to_device_nhwc(torch.stack([torch.as_tensor(trainData[i].diff, dtype=torch.float32) for i in idx]))
+                cond_r = ctx.to_device_nhwc(torch.stack([torch.as_tensor(trainData[i].coarse, dtype=torch.float32) for i in idx]))
             _, cond_f = pick(half, "coarse")                                  # new random conds for the fake half (C13)
             nz = S.next_noise(ctx, half, h * w).view(half, h, w, 1)
             pending.append(tr.step_D(diff, cond_r, nz, cond_f)["confusion"].clone())
@@ -152,12 +163,20 @@ def approxParzen(ds, nsamples, nneighbors):
     c, h, w = S.IMG_DIMENSIONS
     dist_dev, min_dev = ctx.empty(nneighbors), ctx.empty(nsamples)
     G = S.MODEL_G
+    resident = is_resident(ds)
     for n in range(nsamples):
-        example = ds[S.rng.randrange(ds.size())]
-        cond = ctx.to_device_nhwc(torch.as_tensor(example.coarse, dtype=torch.float32).unsqueeze(0).repeat(nneighbors, 1, 1, 1))
+        pick = S.rng.randrange(ds.size())
+        if resident:                        # "one image nneighbors times" and the fine image: two gathers, nothing from the host
+            cond = ds.gather([pick] * nneighbors, "coarse")
+        else:
+            example = ds[pick]
+            cond = ctx.to_device_nhwc(torch.as_tensor(example.coarse, dtype=torch.float32).unsqueeze(0).repeat(nneighbors, 1, 1, 1))
         noise = S.next_noise(ctx, nneighbors, h * w).view(nneighbors, h, w, 1)
         neighbors = G.inner.device_net.forward(G.combine_device(ctx, noise, cond), train=G.inner.train)
-        fine = ctx.to_device_nhwc(torch.as_tensor(example.fine, dtype=torch.float32).unsqueeze(0))
+        if resident:
+            fine = ds.gather([pick], "fine")
+        else:
+            fine = ctx.to_device_nhwc(torch.as_tensor(example.fine, dtype=torch.float32).unsqueeze(0))
         # neighbors:add(condInputs); min_i torch.dist(neighbors[i], fine)  (:322-329) -- one reduction kernel, NHWC throughout
         ctx.check(ctx.lib.fg_parzen_min_dist(ctx.h, neighbors.data_ptr(), cond.data_ptr(), fine.data_ptr(), nneighbors,
                                              c * h * w, dist_dev.data_ptr(), min_dev[n:].data_ptr()))

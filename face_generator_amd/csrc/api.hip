@@ -257,6 +257,18 @@ int fg_nhwc_to_nchw(fg_ctx* ctx, const float* s, float* d, int n, int c, int h, 
     NEED(ctx, ctx && s && d && n >= 0 && c > 0 && h > 0 && w > 0, "bad argument");
     return fg_launch_nhwc_to_nchw(ctx, s, d, n, c, h, w);
 }
+int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int h, int w, int set_layout, const int* idx, int n,
+                     float* out, int out_layout) {
+    NEED(ctx, ctx, "null ctx");
+    if (!set || !idx || !out || n_set < 1 || c < 1 || h < 1 || w < 1 || n < 0 || (set_layout != 0 && set_layout != 1) ||
+        (out_layout != 0 && out_layout != 1))
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_gather_images: bad argument (n_set=%lld c=%d %dx%d n=%d layouts %d -> %d)", n_set, c, h, w, n,
+                          set_layout, out_layout);
+    if ((long long)c * h * w >= (1LL << 31))
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_gather_images: an image of %d x %d x %d floats is 2^31 floats or more", c, h, w);
+    if (n == 0) return FG_OK;
+    return fg_launch_gather_images(ctx, set, n_set, c, h * w, set_layout, idx, n, out, out_layout);
+}
 int fg_rng_uniform(fg_ctx* ctx, uint64_t seed, uint64_t off, float* o, long long n, float lo, float hi) {
     NEED(ctx, ctx && o && n >= 0, "bad argument");
     return fg_launch_rng_uniform(ctx, seed, off, o, n, lo, hi);

@@ -335,6 +335,8 @@ static inline int fg_fold_r(int parity, int d, int pad) {  // floor((parity + d 
 // ---------------------------------------------------------------------------------
 int fg_launch_nchw_to_nhwc(fg_ctx*, const float* src, float* dst, int N, int C, int H, int W);
 int fg_launch_nhwc_to_nchw(fg_ctx*, const float* src, float* dst, int N, int C, int H, int W);
+// out[j] = set[idx[j]]: n images of c x P floats, each side [c][P] (nchw != 0) or [P][c]
+int fg_launch_gather_images(fg_ctx*, const float* set, long long n_set, int c, int P, int set_nchw, const int* idx, int n, float* out, int out_nchw);
 int fg_launch_fill(fg_ctx*, float* p, float v, long long n);
 // column sums of [M][N] -> out[N] = beta*out + sum (two-stage, deterministic). scratch >= 256*N floats
 int fg_launch_colsum(fg_ctx*, const float* x, long long M, int N, float beta, float* out, float* scratch);

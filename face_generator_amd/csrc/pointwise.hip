@@ -33,41 +33,175 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
 }
 
 // ------------------------------------------------------------------ layout
-__global__ void nchw_to_nhwc_kernel(const float* __restrict__ s, float* __restrict__ d, int N, int C, int H, int W) {
-    long long total = (long long)N * C * H * W;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        int c = (int)(i % C);
-        long long t = i / C;
-        int w = (int)(t % W); t /= W;
-        int h = (int)(t % H);
-        int n = (int)(t / H);
-        d[i] = s[(((long long)n * C + c) * H + h) * W + w];
+// fg_gather_images (include/facegen_hip.h): out[j] = set[idx[j]].  The three layout kernels are templates; GATHER = 0 is the
+// instance every earlier entry launches (its body is what it was), GATHER = 1 the gather's.  An image is P = h * w pixels of c
+// channels; a transposing gather walks LDS tiles of TP pixels x up to GI_CT channels, one tile per block and pass (TP = 1024 for
+// c <= 4, 512 up to 8, 256 above: 8 to 32 KB of image per pass where the image has them, which keeps enough loads in flight):
+//   - the channel-major side moves rows: channel ch of the tile is TP consecutive floats of the image (16-byte accesses if VR),
+//     four accesses per lane issued before the first is used;
+//   - the pixel-major side moves the tile's pixels in element order: with c <= GI_CT that is one contiguous run of pn * c floats
+//     (16-byte accesses if VL), above it runs of cn floats at stride c;
+//   - the tile is tile[ch * S + pixel] with S = TP + pad.  Unpadded, the c channels of a pixel share a bank and the element-order
+//     side serialises c-way; the pad the launcher picks leaves at most two lanes of a 32-lane group on a bank for c <= 16 (four
+//     up to 32), and S stays a multiple of 4 so that the row side moves 16 bytes per lane.
+// Index arithmetic is 32-bit inside an image (c * h * w < 2^31) and 64-bit only for the image's base.  No division in the loops:
+// a thread's (pixel, channel) advances by the quotient and remainder of its stride by cn, taken once in front of them.
+#define GI_CT 32
+#define GI_COPY 4096            // floats of one unit of the same-layout gather: 256 lanes x 4 x 16 bytes
+__device__ __forceinline__ float gi_nan() { return __int_as_float(0x7fc00000); }
+// rows of the tile <-> channel rows of the image.  g: the image at (channel c0, pixel p0); P: its row pitch; tsh = log2(TP)
+template <bool TO_LDS, bool VEC>
+__device__ __forceinline__ void gi_rows(float* __restrict__ g, float* __restrict__ tile, int S, int P, int cn, int pn, int tsh, bool live) {
+    constexpr int W = VEC ? 4 : 1;
+    const int sh = VEC ? tsh - 2 : tsh, total = cn << sh;           // slots of W pixels: a row of the tile has 1 << sh of them
+    for (int i0 = threadIdx.x; i0 < total; i0 += 1024) {
+        float4 v[4];
+        int at[4], to[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = i0 + 256 * k, ch = i >> sh, px = (i & ((1 << sh) - 1)) * W;
+            const bool ok = i < total && px < pn;                   // VEC: pn % 4 == 0 and every row 16-byte aligned (P % 4 == 0)
+            at[k] = ok ? ch * P + px : -1;
+            to[k] = ch * S + px;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (at[k] < 0) continue;
+            if constexpr (!TO_LDS) {
+                if constexpr (VEC) v[k] = *reinterpret_cast<const float4*>(tile + to[k]);
+                else v[k].x = tile[to[k]];
+            } else if (!live) v[k] = make_float4(gi_nan(), gi_nan(), gi_nan(), gi_nan());
+            else if constexpr (VEC) v[k] = *reinterpret_cast<const float4*>(g + at[k]);
+            else v[k].x = g[at[k]];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (at[k] < 0) continue;
+            if constexpr (TO_LDS) {
+                if constexpr (VEC) *reinterpret_cast<float4*>(tile + to[k]) = v[k];
+                else tile[to[k]] = v[k].x;
+            } else {
+                if constexpr (VEC) *reinterpret_cast<float4*>(g + at[k]) = v[k];
+                else g[at[k]] = v[k].x;
+            }
+        }
     }
 }
-__global__ void nhwc_to_nchw_kernel(const float* __restrict__ s, float* __restrict__ d, int N, int C, int H, int W) {
-    long long total = (long long)N * C * H * W;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        int w = (int)(i % W);
-        long long t = i / W;
-        int h = (int)(t % H); t /= H;
-        int c = (int)(t % C);
-        int n = (int)(t / C);
-        d[i] = s[(((long long)n * H + h) * W + w) * C + c];
+// the tile's pixels in element order <-> the pixel-major image.  g: the image at (pixel p0, channel c0); c: its pixel pitch.
+// (px, ch): this thread's first element; (q, r): quotient and remainder of its stride (256, or 1024 with VEC) by cn
+template <bool TO_LDS, bool VEC>
+__device__ __forceinline__ void gi_linear(float* __restrict__ g, float* __restrict__ tile, int S, int c, int cn, int pn, int px, int ch,
+                                          int q, int r, bool live) {
+    const int total = pn * cn;
+    if constexpr (VEC) {        // cn == c: one contiguous run, total % 4 == 0, 16-byte aligned
+#pragma unroll 2
+        for (int e = threadIdx.x * 4; e < total; e += 1024) {
+            int a[4], p = px, k = ch;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                a[i] = k * S + p;
+                if (++k == cn) { k = 0; ++p; }
+            }
+            if constexpr (TO_LDS) {
+                const float4 v = live ? *reinterpret_cast<const float4*>(g + e) : make_float4(gi_nan(), gi_nan(), gi_nan(), gi_nan());
+                tile[a[0]] = v.x; tile[a[1]] = v.y; tile[a[2]] = v.z; tile[a[3]] = v.w;
+            } else
+                *reinterpret_cast<float4*>(g + e) = make_float4(tile[a[0]], tile[a[1]], tile[a[2]], tile[a[3]]);
+            px += q; ch += r;
+            if (ch >= cn) { ch -= cn; ++px; }
+        }
+    } else {
+#pragma unroll 2
+        for (int e = threadIdx.x; e < total; e += 256) {
+            if constexpr (TO_LDS) tile[ch * S + px] = live ? g[px * c + ch] : gi_nan();
+            else g[px * c + ch] = tile[ch * S + px];
+            px += q; ch += r;
+            if (ch >= cn) { ch -= cn; ++px; }
+        }
+    }
+}
+// NCHW set -> NHWC out (NCHW_IN) or the reverse, one tile per pass of a block.  P = h * w, upi = tiles per image, TP = 1 << tsh
+template <bool NCHW_IN, bool VR, bool VL>
+__device__ __forceinline__ void gi_transpose(const float* __restrict__ set, float* __restrict__ out, const int* __restrict__ idx,
+                                             long long n_set, int n, int c, int P, int upi, int S, int tsh) {
+    extern __shared__ float4 gi_tile[];                                     // min(c, GI_CT) * S floats
+    float* tile = reinterpret_cast<float*>(gi_tile);
+    const int TP = 1 << tsh, ptiles = (P + TP - 1) >> tsh, cfull = c < GI_CT ? c : GI_CT;
+    constexpr int STEP = VL ? 1024 : 256, T0 = VL ? 4 : 1;
+    const int e0 = (int)threadIdx.x * T0;
+    const int px_f = e0 / cfull, ch_f = e0 - px_f * cfull, q_f = STEP / cfull, r_f = STEP - q_f * cfull;
+    // image j and unit u of it: block b starts at unit b and advances by gridDim.x units
+    int j = (int)blockIdx.x / upi, u = (int)blockIdx.x - j * upi;
+    const int dj = (int)gridDim.x / upi, du = (int)gridDim.x - dj * upi;
+    for (; j < n; j += dj, u += du) {
+        if (u >= upi) { u -= upi; ++j; if (j >= n) break; }
+        int ct = 0, pt = u;
+        if (upi != ptiles) { ct = u / ptiles; pt = u - ct * ptiles; }       // c > GI_CT only: several channel chunks
+        const int c0 = ct * GI_CT, p0 = pt << tsh;
+        const int cn = c - c0 < GI_CT ? c - c0 : GI_CT, pn = P - p0 < TP ? P - p0 : TP;
+        int px = px_f, ch = ch_f, q = q_f, r = r_f;
+        if (cn != cfull) { px = e0 / cn; ch = e0 - px * cn; q = STEP / cn; r = STEP - q * cn; }   // the last, narrower chunk
+        const int i = idx[j];
+        const bool live = i >= 0 && (long long)i < n_set;                  // outside the set: nothing is read, the image is NaN
+        const long long E = (long long)c * P;
+        float* src = const_cast<float*>(set) + (live ? (long long)i * E : 0);
+        float* dst = out + (long long)j * E;
+        __syncthreads();                                                    // the tile of the pass before has been read
+        if constexpr (NCHW_IN) gi_rows<true, VR>(src + c0 * P + p0, tile, S, P, cn, pn, tsh, live);
+        else gi_linear<true, VL>(src + p0 * c + c0, tile, S, c, cn, pn, px, ch, q, r, live);
+        __syncthreads();
+        if constexpr (NCHW_IN) gi_linear<false, VL>(dst + p0 * c + c0, tile, S, c, cn, pn, px, ch, q, r, true);
+        else gi_rows<false, VR>(dst + c0 * P + p0, tile, S, P, cn, pn, tsh, true);
+    }
+}
+template <int GATHER = 0, bool VR = false, bool VL = false>
+__global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ s, float* __restrict__ d, int N, int C, int H, int W,
+                                                           const int* __restrict__ idx, long long n_set, int S, int tsh) {
+    if constexpr (GATHER) {
+        gi_transpose<true, VR, VL>(s, d, idx, n_set, N, C, H, W, S, tsh);        // H: pixels of an image, W: tiles of an image
+    } else {
+        long long total = (long long)N * C * H * W;
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+             i += (long long)gridDim.x * blockDim.x) {
+            int c = (int)(i % C);
+            long long t = i / C;
+            int w = (int)(t % W); t /= W;
+            int h = (int)(t % H);
+            int n = (int)(t / H);
+            d[i] = s[(((long long)n * C + c) * H + h) * W + w];
+        }
+    }
+}
+template <int GATHER = 0, bool VR = false, bool VL = false>
+__global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restrict__ s, float* __restrict__ d, int N, int C, int H, int W,
+                                                           const int* __restrict__ idx, long long n_set, int S, int tsh) {
+    if constexpr (GATHER) {
+        gi_transpose<false, VR, VL>(s, d, idx, n_set, N, C, H, W, S, tsh);
+    } else {
+        long long total = (long long)N * C * H * W;
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+             i += (long long)gridDim.x * blockDim.x) {
+            int w = (int)(i % W);
+            long long t = i / W;
+            int h = (int)(t % H); t /= H;
+            int c = (int)(t % C);
+            int n = (int)(t / C);
+            d[i] = s[(((long long)n * H + h) * W + w) * C + c];
+        }
     }
 }
 int fg_launch_nchw_to_nhwc(fg_ctx* ctx, const float* s, float* d, int N, int C, int H, int W) {
     long long n = (long long)N * C * H * W;
     if (n == 0) return FG_OK;
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, FG_GRID(n, 256), dim3(256), 0, ctx->stream, s, d, N, C, H, W);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, FG_GRID(n, 256), dim3(256), 0, ctx->stream, s, d, N, C, H, W, (const int*)nullptr, 0LL, 0, 0);
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }
 int fg_launch_nhwc_to_nchw(fg_ctx* ctx, const float* s, float* d, int N, int C, int H, int W) {
     long long n = (long long)N * C * H * W;
     if (n == 0) return FG_OK;
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, FG_GRID(n, 256), dim3(256), 0, ctx->stream, s, d, N, C, H, W);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel, FG_GRID(n, 256), dim3(256), 0, ctx->stream, s, d, N, C, H, W, (const int*)nullptr, 0LL, 0, 0);
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }
@@ -1508,19 +1642,80 @@ int fg_launch_sum_parts(fg_ctx* ctx, const FgRowParts& a, float* out, long long 
     return FG_OK;
 }
 // plain device copy (hipMemcpyAsync's blit kernel took ~0.4 ms for a 3 MB batch half on this stack: a 7 % tax on the c2f step)
-__global__ __launch_bounds__(256) void copy_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n) {
-    const long long n4 = n >> 2;
-    const bool al = (((size_t)src | (size_t)dst) & 15) == 0;
-    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
-    if (al) {
-        for (long long i = i0; i < n4; i += step) ((float4*)dst)[i] = ((const float4*)src)[i];
-        for (long long i = (n4 << 2) + i0; i < n; i += step) dst[i] = src[i];
-    } else
-        for (long long i = i0; i < n; i += step) dst[i] = src[i];
+template <int GATHER = 0, bool VEC = false>
+__global__ __launch_bounds__(256) void copy_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n,
+                                                   const int* __restrict__ idx, long long n_set, int count, int upi) {
+    if constexpr (GATHER) {
+        // fg_gather_images, same layout on both sides: n floats per image, unit = GI_COPY floats of one image, upi units per image
+        const int E = (int)n;
+        int j = (int)blockIdx.x / upi, u = (int)blockIdx.x - j * upi;
+        const int dj = (int)gridDim.x / upi, du = (int)gridDim.x - dj * upi;
+        for (; j < count; j += dj, u += du) {
+            if (u >= upi) { u -= upi; ++j; if (j >= count) break; }
+            const int i = idx[j];
+            const bool live = i >= 0 && (long long)i < n_set;
+            const float* __restrict__ s = src + (live ? (long long)i * n : 0);
+            float* __restrict__ d = dst + (long long)j * n;
+            const int e0 = u * GI_COPY, len = E - e0 < GI_COPY ? E - e0 : GI_COPY;
+            s += e0; d += e0;
+            if constexpr (VEC) {
+                for (int e = (int)threadIdx.x * 4; e < len; e += 1024)
+                    *reinterpret_cast<float4*>(d + e) = live ? *reinterpret_cast<const float4*>(s + e) : make_float4(gi_nan(), gi_nan(), gi_nan(), gi_nan());
+            } else {
+                for (int e = (int)threadIdx.x; e < len; e += 256) d[e] = live ? s[e] : gi_nan();
+            }
+        }
+    } else {
+        const long long n4 = n >> 2;
+        const bool al = (((size_t)src | (size_t)dst) & 15) == 0;
+        const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+        if (al) {
+            for (long long i = i0; i < n4; i += step) ((float4*)dst)[i] = ((const float4*)src)[i];
+            for (long long i = (n4 << 2) + i0; i < n; i += step) dst[i] = src[i];
+        } else
+            for (long long i = i0; i < n; i += step) dst[i] = src[i];
+    }
 }
 int fg_launch_copy(fg_ctx* ctx, const float* src, float* dst, long long n) {
     if (n == 0) return FG_OK;
-    hipLaunchKernelGGL(copy_kernel, FG_GRID((n + 3) / 4, 256), dim3(256), 0, ctx->stream, src, dst, n);
+    hipLaunchKernelGGL(copy_kernel, FG_GRID((n + 3) / 4, 256), dim3(256), 0, ctx->stream, src, dst, n, (const int*)nullptr, 0LL, 0, 0);
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
+// fg_gather_images: out[j] = set[idx[j]] for n images of c x P floats.  c == 1 or P == 1: the two layouts are one order
+int fg_launch_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int P, int set_nchw, const int* idx, int n, float* out,
+                            int out_nchw) {
+    const long long E = (long long)c * P;
+    const bool a_set = ((size_t)set & 15) == 0, a_out = ((size_t)out & 15) == 0;
+    if (set_nchw == out_nchw || c == 1 || P == 1) {
+        const int upi = (int)((E + GI_COPY - 1) / GI_COPY);
+        const long long units = (long long)n * upi;
+        if (a_set && a_out && E % 4 == 0)
+            hipLaunchKernelGGL((copy_kernel<1, true>), FG_GRID(units, 1), dim3(256), 0, ctx->stream, set, out, E, idx, n_set, n, upi);
+        else
+            hipLaunchKernelGGL((copy_kernel<1, false>), FG_GRID(units, 1), dim3(256), 0, ctx->stream, set, out, E, idx, n_set, n, upi);
+        FG_CHECK_LAUNCH(ctx);
+        return FG_OK;
+    }
+    // a tile holds TP = 1 << tsh pixels of up to GI_CT channels: 8 to 32 KB of image per pass, and no more 256-pixel quarters than the image has
+    const int cfull = c < GI_CT ? c : GI_CT;
+    int tsh = cfull <= 4 ? 10 : cfull <= 8 ? 9 : 8;
+    while (tsh > 8 && (1 << (tsh - 1)) >= P) --tsh;
+    const int upi = ((P + (1 << tsh) - 1) >> tsh) * ((c + GI_CT - 1) / GI_CT);
+    const long long units = (long long)n * upi;
+    // the row pitch of the LDS tile (see gi_transpose): S % 32 spreads the channels of a pixel over the banks
+    const int S = (1 << tsh) + (c <= 2 ? 16 : c <= 4 ? 8 : 4);
+    const size_t lds = (size_t)cfull * S * sizeof(float);
+    const bool vr = (set_nchw ? a_set : a_out) && P % 4 == 0;               // the channel-major side moves 16 bytes per lane
+    const bool vl = (set_nchw ? a_out : a_set) && E % 4 == 0 && c <= GI_CT; // the pixel-major side does
+    if (set_nchw && vr && vl) hipLaunchKernelGGL((nchw_to_nhwc_kernel<1, true, true>), FG_GRID(units, 1), dim3(256), lds, ctx->stream, set, out, n, c, P, upi, idx, n_set, S, tsh);
+    if (set_nchw && vr && !vl) hipLaunchKernelGGL((nchw_to_nhwc_kernel<1, true, false>), FG_GRID(units, 1), dim3(256), lds, ctx->stream, set, out, n, c, P, upi, idx, n_set, S, tsh);
+    if (set_nchw && !vr && vl) hipLaunchKernelGGL((nchw_to_nhwc_kernel<1, false, true>), FG_GRID(units, 1), dim3(256), lds, ctx->stream, set, out, n, c, P, upi, idx, n_set, S, tsh);
+    if (set_nchw && !vr && !vl) hipLaunchKernelGGL((nchw_to_nhwc_kernel<1, false, false>), FG_GRID(units, 1), dim3(256), lds, ctx->stream, set, out, n, c, P, upi, idx, n_set, S, tsh);
+    if (!set_nchw && vr && vl) hipLaunchKernelGGL((nhwc_to_nchw_kernel<1, true, true>), FG_GRID(units, 1), dim3(256), lds, ctx->stream, set, out, n, c, P, upi, idx, n_set, S, tsh);
+    if (!set_nchw && vr && !vl) hipLaunchKernelGGL((nhwc_to_nchw_kernel<1, true, false>), FG_GRID(units, 1), dim3(256), lds, ctx->stream, set, out, n, c, P, upi, idx, n_set, S, tsh);
+    if (!set_nchw && !vr && vl) hipLaunchKernelGGL((nhwc_to_nchw_kernel<1, false, true>), FG_GRID(units, 1), dim3(256), lds, ctx->stream, set, out, n, c, P, upi, idx, n_set, S, tsh);
+    if (!set_nchw && !vr && !vl) hipLaunchKernelGGL((nhwc_to_nchw_kernel<1, false, false>), FG_GRID(units, 1), dim3(256), lds, ctx->stream, set, out, n, c, P, upi, idx, n_set, S, tsh);
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }

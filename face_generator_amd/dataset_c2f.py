@@ -53,6 +53,40 @@ def toResult(fineImages, coarseScale, fineScale, ctx=None):
     return Result(fine.cpu(), coarse.cpu(), diff.cpu())
 
 
+class ResidentResult:
+    """Result with the three sets resident in HBM: .fine / .coarse / .diff are runtime.DeviceDataset objects (gather() feeds the
+    c2f steps without a host round trip); size() and [i] behave as Result's do, [i] by three small copies to the host."""
+
+    def __init__(self, fine, coarse, diff):
+        self.fine, self.coarse, self.diff = fine, coarse, diff
+
+    def size(self):
+        return self.fine.size()
+
+    def __len__(self):
+        return self.size()
+
+    def gather(self, indices, field, layout="nhwc", out=None):
+        return getattr(self, field).gather(indices, layout=layout, out=out)
+
+    def __getitem__(self, i):
+        return Example(self.coarse[i], self.fine[i], self.diff[i])
+
+
+def toResultResident(fineImages, coarseScale, fineScale, ctx=None):
+    """toResult that leaves the epoch's set on the device: fineImages (host or device [N, C, fineScale, fineScale]) is uploaded
+    once, coarse and diff are computed once by fg_c2f_coarse_diff, and all three stay in HBM as DeviceDatasets."""
+    from . import ops
+    from .runtime import get_context, DeviceDataset
+    ctx = ctx or get_context()
+    fine = torch.as_tensor(fineImages)
+    if fine.dim() != 4 or fine.shape[-1] != fineScale or fine.shape[-2] != fineScale:
+        raise ValueError("toResultResident: fine images must be [N, C, %d, %d]" % (fineScale, fineScale))
+    fine = DeviceDataset(ctx, fine)
+    coarse, diff = ops.c2f_coarse_diff(fine.images, coarseScale, layout="nchw", ctx=ctx)
+    return ResidentResult(fine, DeviceDataset(ctx, coarse), DeviceDataset(ctx, diff))
+
+
 def toResultDevice(fine_nhwc, coarseScale, ctx=None):
     """The same step for a batch that already lives in HBM in the library's activation layout [N][S][S][C]: -> (coarse, diff) device
     tensors, the inputs of TrainerC2F.step_D / step_G."""

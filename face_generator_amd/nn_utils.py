@@ -5,7 +5,7 @@ import os
 import torch
 
 from . import nn
-from .runtime import get_context
+from .runtime import get_context, is_resident
 from .state import S
 
 
@@ -111,13 +111,20 @@ def findClosestNeighboursOf(images, trainingSet, chunk_rows=8192, ctx=None):
     images: device NHWC [q][H][W][C]; they are converted to NCHW once, so that the set streams in the CHW order in which it is
     stored.  trainingSet: a [N][C][H][W] float32 tensor or array, or any object with size() and [i] as dataset.lua returns.
     -> ([(index, distance)] per image, the q neighbour images [q][C][H][W] gathered on the host by index).  The first of equally
-    near training images wins (the strict `<` of sample.lua:142)."""
+    near training images wins (the strict `<` of sample.lua:142).  A runtime.DeviceDataset is searched where it lies: nothing is
+    uploaded, and the neighbour images come back as a device tensor gathered by the device's own best_index."""
     from .runtime import NearestSearch
     ctx = ctx or get_context()
     N = trainingSet.size() if callable(getattr(trainingSet, "size", None)) and not torch.is_tensor(trainingSet) else len(trainingSet)
     if N < 1:
         raise ValueError("findClosestNeighboursOf: the training set is empty")
     search = NearestSearch(ctx, ctx.to_nchw(images))
+    if is_resident(trainingSet):            # runtime.DeviceDataset: the rows stream from HBM, the neighbours are gathered there
+        for lo in range(0, N, chunk_rows):
+            search.update(trainingSet.rows(lo, min(lo + chunk_rows, N)), lo)
+        index, dist = search.result()
+        found = [(int(i), float(d)) for i, d in zip(index.tolist(), dist.tolist())]
+        return found, trainingSet.gather(search.best_index, layout="nchw")
     for lo in range(0, N, chunk_rows):
         search.update(_set_rows(trainingSet, lo, min(lo + chunk_rows, N)), lo)
     index, dist = search.result()

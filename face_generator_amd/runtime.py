@@ -725,3 +725,73 @@ class NearestSearch:
             return torch.full((self.q,), -1, dtype=torch.int32), torch.full((self.q,), float("inf"))
         both = torch.cat([self.best_index.view(torch.float32), self.best_dist]).cpu()
         return both[:self.q].view(torch.int32).clone(), both[self.q:].clone()
+
+
+def is_resident(dataset):
+    """does the dataset offer gather(), i.e. does it live in HBM?  (A torch tensor has a gather of its own: a host set.)"""
+    return not torch.is_tensor(dataset) and callable(getattr(dataset, "gather", None))
+
+
+class DeviceDataset:
+    """A training set that lives in HBM (train.lua loads N_epoch images once per epoch, adversarial.lua:245 indexes them):
+    [N][C][H][W] float32 on the device, the reference's layout and the order NearestSearch streams.  It keeps the reference's
+    dataset protocol -- size(), len(), ds[i] -> host CHW tensor (dataset.lua:66-69) -- and adds gather(): dataset[i] for a whole
+    batch of indices as one launch of fg_gather_images, in the layout the steps and the nets take."""
+
+    def __init__(self, ctx, images, scale=None):
+        """images: host or device float32 [N][C][H][W], tensor or array.  scale: side to scale every image to on the device
+        (image.scale, dataset.lua:95) when H, W differ from it."""
+        self.ctx, self.lib = ctx, ctx.lib
+        x = torch.as_tensor(images)
+        if x.dim() != 4 or x.shape[0] < 1:
+            raise FgError("DeviceDataset: images must be [N][C][H][W] with N >= 1, got %s" % (tuple(x.shape),))
+        x = x.to(dtype=torch.float32).to(ctx.device).contiguous()
+        if scale is not None and (x.shape[2] != scale or x.shape[3] != scale):
+            from . import ops
+            x = ops.scale_bilinear(x, int(scale), int(scale), layout="nchw", ctx=ctx)
+        self.images = x
+        self.n, self.c, self.h, self.w = (int(v) for v in x.shape)
+
+    def size(self):
+        return self.n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        i = int(i)
+        if i < 0 or i >= self.n:
+            raise IndexError("DeviceDataset: index %d outside [0, %d)" % (i, self.n))
+        return self.images[i].cpu()
+
+    def rows(self, lo, hi):
+        """images lo .. hi-1 as a device view [hi - lo][C][H][W] (no copy)"""
+        return self.images[lo:hi]
+
+    def indices(self, indices):
+        """host indices (range-checked here, one upload) or a device int32 tensor (used as it is) -> device int32 [n]"""
+        if isinstance(indices, torch.Tensor) and indices.device.type != "cpu":
+            if indices.dtype != torch.int32 or indices.dim() != 1:
+                raise FgError("DeviceDataset.gather: device indices must be a 1-d int32 tensor")
+            return indices.contiguous()
+        host = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
+        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= self.n):
+            raise IndexError("DeviceDataset.gather: index outside [0, %d)" % self.n)
+        return host.to(torch.int32).to(self.ctx.device)
+
+    def gather(self, indices, layout="nhwc", out=None):
+        """-> device [n][H][W][C] ("nhwc", what step_D / step_G and the nets take) or [n][C][H][W] ("nchw") with out[j] =
+        dataset[indices[j]]; repeated indices are legal."""
+        if layout not in ("nhwc", "nchw"):
+            raise FgError("DeviceDataset.gather: layout must be 'nhwc' or 'nchw'")
+        idx = self.indices(indices)
+        n = int(idx.numel())
+        shape = (n, self.h, self.w, self.c) if layout == "nhwc" else (n, self.c, self.h, self.w)
+        if out is None:
+            out = self.ctx.empty(*shape)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * self.c * self.h * self.w:
+            raise FgError("DeviceDataset.gather: out must be a contiguous float32 tensor of %d elements" % (n * self.c * self.h * self.w))
+        if n:                               # (an empty tensor has no address to hand over)
+            self.ctx.check(self.lib.fg_gather_images(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1,
+                                                     idx.data_ptr(), n, out.data_ptr(), 0 if layout == "nhwc" else 1))
+        return out.view(*shape)

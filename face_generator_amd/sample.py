@@ -17,7 +17,7 @@ import os
 import torch
 
 from . import nn_utils
-from .runtime import Sampler, get_context
+from .runtime import DeviceDataset, Sampler, get_context
 from .state import S
 
 N_IMAGES = 1024                      # sample.lua:80
@@ -159,7 +159,8 @@ def main(opt=None, ctx=None):
     sm.set_seed(opt["seed"], 0)
     files = output_files(opt)
     per_run = len(STEMS) + (1 if opt["neighbours"] else 0)
-    trainingSet = loadTrainingSet(opt["trainingSet"], dims, ctx) if opt["neighbours"] else None
+    # the set goes to HBM once, in front of the run loop: every run searches it there (runtime.DeviceDataset)
+    trainingSet = DeviceDataset(ctx, loadTrainingSet(opt["trainingSet"], dims, ctx)) if opt["neighbours"] else None
     print("Sampling...")
     for run in range(opt["runs"]):
         sm.sample(N_IMAGES)

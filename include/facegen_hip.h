@@ -514,6 +514,25 @@ size_t fg_nearest_workspace_bytes(int q, int n);
 int fg_nearest_update(fg_ctx* ctx, const float* queries, int q, const float* rows, int n, long long elems, long long first_index,
                       int first, double* best_d2, int* best_index, float* best_dist, void* scratch, size_t scratch_bytes);
 
+/* ---- dataset[i] for a set that lives in HBM (dataset.lua:66-69, dataset_c2f.lua:65-106; adversarial.lua:245 indexes the epoch's
+ *      set once per sample): out[j] = set[idx[j]], j = 0 .. n-1, in one launch. ----
+ * set: n_set images of c * h * w device floats, [n_set][c][h][w] (set_layout 1: the reference's tensors, and the order
+ *   fg_nearest_update streams) or [n_set][h][w][c] (set_layout 0).  out: n images in out_layout, the convention of the `layout`
+ *   argument of fg_scale_bilinear (0 is what fg_step_D's real / cond_* and the nets take).  All four combinations: two copy rows,
+ *   two transpose through LDS (runs that are contiguous in the source are read, runs that are contiguous in the destination written).
+ * idx: device int[n].  Repeated indices are legal (approxParzen's "one image nneighbors times" is one call).  An index outside
+ *   [0, n_set) reads nothing and fills its image with quiet NaN (0x7fc00000): the device cannot refuse, and nothing outside `set`
+ *   is ever read.  Nothing outside out[0 .. n * c * h * w) is written.
+ * Sizes: n_set * c * h * w may exceed 2^31 floats (the image's base offset is 64-bit); c * h * w < 2^31.  Any c, h, w >= 1.
+ * n == 0: FG_OK, nothing is launched.  NULL pointers, n_set / c / h / w < 1, n < 0, a layout other than 0 / 1 or an image of 2^31
+ *   floats or more: FG_ERR_INVALID, nothing is launched.
+ * Alignment: 4 bytes are enough.  16-byte accesses are used on a side whose base is 16-byte aligned and whose rows allow it
+ *   (h * w % 4 == 0 on an NCHW side, c * h * w % 4 == 0 on an NHWC side and for a copy), 4-byte accesses of the same elements
+ *   otherwise -- the rule fg_nearest_update states.  No scratch, no atomics, no synchronisation: one launch on the context's
+ *   stream. */
+int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int h, int w, int set_layout, const int* idx, int n,
+                     float* out, int out_layout);
+
 /* ---- the c2f data step in front of the train closure (dataset_c2f.lua:49-61, `dataset._toResult`) ----
  * fg_scale_bilinear = image.scale(src, width, height) of the Torch7 `image` package (default mode 'bilinear'; un-vendored luarocks
  * dependency, restated in oracle/image_scale.py): width pass then height pass; per axis up-scaling interpolates with

@@ -45,6 +45,13 @@ local function pick(data, n, field, c, h, w)
     return out
 end
 
+-- the same `n` math.random draws as 1-based indices, for a set that is gathered on the device (FG.Dataset:gather)
+local function picks(data, n)
+    local out = {}
+    for i = 1, n do out[i] = math.random(data:size()) end
+    return out
+end
+
 function adversarial.train(trainData)
     if not (inner_of(MODEL_G) and inner_of(MODEL_D)) then return reference_impl().train(trainData) end
     EPOCH = EPOCH or 1
@@ -55,6 +62,7 @@ function adversarial.train(trainData)
     local g = gan()
     local c, h, w = IMG_DIMENSIONS[1], IMG_DIMENSIONS[2], IMG_DIMENSIONS[3]
     local cc = COND_DIM[1]
+    local resident = FG.isDataset(trainData.coarse)          -- FG.residentResult: .fine / .coarse / .diff are FG.Datasets
     -- one device slot of 8 counts per D closure of the epoch, read once after the loop (no host sync, no allocation inside it)
     local maxClosures = (math.floor((N_epoch - 1) / dataBatchSize) + 1) * OPT.D_iterations
     local slots, nslots = FG.DeviceTensor(8 * maxClosures), 0
@@ -71,22 +79,33 @@ function adversarial.train(trainData)
 
         for k = 1, OPT.D_iterations do
             -- (1.1) real data: ONE pick gives .diff and .coarse (adversarial_c2f.lua:128-133)
-            local diff, condR = torch.FloatTensor(half, c, h, w), torch.FloatTensor(half, cc, h, w)
-            for i = 1, half do
-                local ex = trainData[math.random(trainData:size())]
-                diff[i] = ex.diff; condR[i] = ex.coarse
-            end
-            -- (1.2) sampled data: new random conditionings (:137-142); G's forward on them runs inside fg_step_D (TRAIN mode)
-            local condF = pick(trainData, half, 'coarse', cc, h, w)
             g:configure('D', OPT, OPTSTATE)
-            g:stepD(thisBatchSize, FG.to_device_nhwc(diff), FG.to_device_nhwc(condR), FG.to_device_nhwc(condF), false)
+            if resident then                                  -- FG.residentResult: the same picks, gathered in HBM (FG.gatherImages)
+                local diffDev, idx = trainData.diff:gather(picks(trainData, half))
+                local condRDev = trainData.coarse:gather(idx, half)
+                local condFDev = trainData.coarse:gather(picks(trainData, half))      -- (1.2)
+                g:stepD(thisBatchSize, diffDev, condRDev, condFDev, false)
+            else
+                local diff, condR = torch.FloatTensor(half, c, h, w), torch.FloatTensor(half, cc, h, w)
+                for i = 1, half do
+                    local ex = trainData[math.random(trainData:size())]
+                    diff[i] = ex.diff; condR[i] = ex.coarse
+                end
+                -- (1.2) sampled data: new random conditionings (:137-142); G's forward on them runs inside fg_step_D (TRAIN mode)
+                local condF = pick(trainData, half, 'coarse', cc, h, w)
+                g:stepD(thisBatchSize, FG.to_device_nhwc(diff), FG.to_device_nhwc(condR), FG.to_device_nhwc(condF), false)
+            end
             g:confusionInto(slots, nslots); nslots = nslots + 1
         end
 
         for k = 1, OPT.G_iterations do
-            local cond = pick(trainData, thisBatchSize, 'coarse', cc, h, w)      -- :165-169
             g:configure('G', OPT, OPTSTATE)
-            g:stepG(thisBatchSize, FG.to_device_nhwc(cond), false)
+            if resident then
+                g:stepG(thisBatchSize, (trainData.coarse:gather(picks(trainData, thisBatchSize))), false)
+            else
+                local cond = pick(trainData, thisBatchSize, 'coarse', cc, h, w)      -- :165-169
+                g:stepG(thisBatchSize, FG.to_device_nhwc(cond), false)
+            end
         end
         xlua.progress(t + thisBatchSize, N_epoch)
     end
@@ -144,15 +163,21 @@ function adversarial.approxParzen(ds, nsamples, nneighbors)
     adversarial.parzen_offset = adversarial.parzen_offset or 0
     for n = 1, nsamples do
         xlua.progress(n, nsamples)
-        local example = ds[math.random(ds:size())]
-        local condInputs = torch.FloatTensor(nneighbors, cc, h, w)
-        for i = 1, nneighbors do condInputs[i] = example.coarse end
-        local cond = FG.to_device_nhwc(condInputs)
+        local cond, fine
+        if FG.isDataset(ds.coarse) then                       -- "one image nneighbors times" is one gather of a repeated index
+            local at, rep = math.random(ds:size()), {}
+            for i = 1, nneighbors do rep[i] = at end
+            cond, fine = ds.coarse:gather(rep), ds.fine:gather({at})
+        else
+            local example = ds[math.random(ds:size())]
+            local condInputs = torch.FloatTensor(nneighbors, cc, h, w)
+            for i = 1, nneighbors do condInputs[i] = example.coarse end
+            cond, fine = FG.to_device_nhwc(condInputs), FG.to_device_nhwc(example.fine:float():view(1, c, h, w))
+        end
         FG.check(C.fg_rng_uniform(FG.ctx, FG.seed, adversarial.parzen_offset, noise.ptr, npix, -1, 1))   -- noiseInputs:uniform(-1, 1)
         adversarial.parzen_offset = adversarial.parzen_offset + math.ceil(npix / 4)
         FG.check(C.fg_concat_channels(FG.ctx, noise.ptr, cond.ptr, joined.ptr, npix, 1, cc))              -- nn.JoinTable(2, 2)
         local neighbors = dnG:forward(joined, nneighbors)                                                   -- mode as the reference leaves it
-        local fine = FG.to_device_nhwc(example.fine:float():view(1, c, h, w))
         -- neighbors:add(condInputs); dist = min_i torch.dist(neighbors[i], fine)  (:321-329): one reduction kernel, NHWC throughout
         FG.check(C.fg_parzen_min_dist(FG.ctx, neighbors, cond.ptr, fine.ptr, nneighbors, c * h * w, dist_dev.ptr, min_dev.ptr + (n - 1)))
     end

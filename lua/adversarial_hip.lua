@@ -42,6 +42,7 @@ function adversarial.train(dataset, maxAccuracyD, accsInterval)
     local g = gan()
     local countTrainedD, countNotTrainedD = 0, 0
     local c, h, w = IMG_DIMENSIONS[1], IMG_DIMENSIONS[2], IMG_DIMENSIONS[3]
+    local resident = FG.isDataset(dataset)       -- FG.Dataset: dataset[i] for a batch is FG.gatherImages on the device
     local useGate = maxAccuracyD <= 1.0          -- D_maxAcc = 1.01 (train.lua:37) can never fire: the update stays inside the step
     local counts = {0, 0, 0, 0}
     -- no gate: one device slot of 8 counts per D closure of the epoch, allocated ONCE here (hipMalloc is a blocking runtime call:
@@ -61,10 +62,18 @@ function adversarial.train(dataset, maxAccuracyD, accsInterval)
 
         for k = 1, OPT.D_iterations do
             -- (1.1) real data: math.random picks (adversarial.lua:244-249); (1.2) the fakes are drawn inside fg_step_D
-            local real = torch.FloatTensor(half, c, h, w)
-            for i = 1, half do real[i] = dataset[math.random(dataset:size())] end
+            local realDev
+            if resident then                                  -- the set lives in HBM: the same picks, one gather there
+                local picks = {}
+                for i = 1, half do picks[i] = math.random(dataset:size()) end
+                realDev = dataset:gather(picks)
+            else
+                local real = torch.FloatTensor(half, c, h, w)
+                for i = 1, half do real[i] = dataset[math.random(dataset:size())] end
+                realDev = FG.to_device_nhwc(real)
+            end
             g:configure('D', OPT, OPTSTATE)
-            g:stepD(thisBatchSize, FG.to_device_nhwc(real), nil, nil, useGate)
+            g:stepD(thisBatchSize, realDev, nil, nil, useGate)
             if useGate then
                 -- CONFUSION:add(c, targets[i] + 1) of adversarial.lua:112-117 and the gate of :124-178: the counts of the GLOBAL
                 -- batch (host read, 32 bytes), the accuracy history, then the update -- or not

@@ -147,6 +147,7 @@ int fg_sample(fg_sampler* s, int n, const float* noise);
 int fg_parzen_min_dist(fg_ctx* ctx, const float* gen, const float* cond, const float* fine, int n, long long elems, float* dist, float* min_out);
 size_t fg_nearest_workspace_bytes(int q, int n);
 int fg_nearest_update(fg_ctx* ctx, const float* queries, int q, const float* rows, int n, long long elems, long long first_index, int first, double* best_d2, int* best_index, float* best_dist, void* scratch, size_t scratch_bytes);
+int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int h, int w, int set_layout, const int* idx, int n, float* out, int out_layout);
 int fg_scale_bilinear(fg_ctx* ctx, const float* src, float* dst, int n, int c, int hs, int ws, int hd, int wd, int layout);
 int fg_c2f_coarse_diff(fg_ctx* ctx, const float* fine, float* coarse, float* diff, float* tmp, int n, int c, int s, int cs, int layout);
 size_t fg_conv2d_workspace_bytes(int batch, int h, int w, int cin, int cout, int k, int upsample2x);
@@ -796,6 +797,61 @@ function Nearest:result()
     local indices, dists = {}, {}
     for j = 1, q do indices[j], dists[j] = host[j - 1], dist[j - 1] end
     return indices, dists
+end
+
+-- (v) the training set resident in HBM (train.lua loads N_epoch images per epoch; adversarial.lua:245 indexes them) ---------------------
+-- fg_gather_images: out[j] = set[idx[j]].  set: DeviceTensor [nSet][c][h][w] (setLayout 1) or [nSet][h][w][c] (0); idx: device int32
+-- (M.indexTensor), 0-based; out: DeviceTensor of n * c * h * w floats in outLayout (0 = NHWC, what the steps and the nets take)
+function M.gatherImages(set, nSet, c, h, w, setLayout, idx, n, out, outLayout)
+    check(C.fg_gather_images(ctx, set.ptr, nSet, c, h, w, setLayout, ffi.cast('const int*', idx.ptr), n, out.ptr, outLayout))
+    return out
+end
+-- FG.Dataset(images): a host FloatTensor [N][C][H][W] uploaded once.  It keeps dataset.lua's protocol -- ds:size(), ds[i] -> host CHW
+-- FloatTensor (1-based, one small copy) -- and adds ds:gather(picks): the batch {ds[picks[1]], ...} as a device NHWC tensor, one launch
+local Dataset = {}
+Dataset.__index = function(self, k)
+    if type(k) == 'number' then return Dataset.get(self, k) end
+    return Dataset[k]
+end
+function M.Dataset(images)
+    assert(images:dim() == 4 and images:size(1) >= 1, 'FG.Dataset: [N][C][H][W] with N >= 1')
+    return setmetatable({images = M.DeviceTensor(images:nElement()):copy(images:float()), n = images:size(1), c = images:size(2),
+                         h = images:size(3), w = images:size(4)}, Dataset)
+end
+function M.isDataset(x) return type(x) == 'table' and getmetatable(x) == Dataset end
+function Dataset:size() return self.n end
+function Dataset:get(i)
+    assert(i >= 1 and i <= self.n, 'FG.Dataset: index out of range')
+    local e = self.c * self.h * self.w
+    local t = torch.FloatTensor(self.c, self.h, self.w)
+    check(C.fg_d2h(ctx, t:data(), self.images.ptr + (i - 1) * e, e * 4))
+    return t
+end
+-- picks: a Lua table of 1-based indices (range-checked here, one upload), or a DeviceTensor of 0-based int32 with its count n
+function Dataset:gather(picks, n, outLayout)
+    local idx = picks
+    if not picks.ptr then
+        n = #picks
+        local zero = {}
+        for i = 1, n do
+            assert(picks[i] >= 1 and picks[i] <= self.n, 'FG.Dataset:gather: index out of range')
+            zero[i] = picks[i] - 1
+        end
+        idx = M.indexTensor(zero)
+    end
+    local out = M.DeviceTensor(n * self.c * self.h * self.w)
+    return M.gatherImages(self.images, self.n, self.c, self.h, self.w, 1, idx, n, out, outLayout or 0), idx
+end
+-- dataset._toResult (dataset_c2f.lua:49-63) with the three sets left in HBM: {fine, coarse, diff} as FG.Datasets, :size(), [i]
+local Resident = {}
+Resident.__index = function(self, k)
+    if type(k) == 'number' then return {coarse = self.coarse[k], fine = self.fine[k], diff = self.diff[k]} end
+    return Resident[k]
+end
+function Resident:size() return self.fine:size() end
+function M.residentResult(fineImages, coarseScale)
+    local coarse, diff = M.coarseDiff(fineImages, coarseScale)
+    return setmetatable({fine = M.Dataset(fineImages), coarse = M.Dataset(coarse), diff = M.Dataset(diff)}, Resident)
 end
 
 return M

@@ -95,18 +95,18 @@ function sample.neighboursGrid(s, k)
     -- the training set is stored CHW: convert the k queries once and stream the set as it is
     local queries = FG.DeviceTensor(k * elems)
     FG.check(FG.C.fg_nhwc_to_nchw(FG.ctx, both.ptr, queries.ptr, k, c, h, w))
-    local data = DATASET.loadImages(0, 9999999).data
-    local N = data:size(1)
+    -- the set goes to HBM once (FG.Dataset) and every run searches it there: no upload per run, the neighbours gathered by index
+    sample.trainingSet = sample.trainingSet or FG.Dataset(DATASET.loadImages(0, 9999999).data)
+    local set = sample.trainingSet
+    local N = set:size()
     local search = FG.Nearest(queries, k, elems)
     for first = 0, N - 1, sample.chunkRows do
         local n = math.min(sample.chunkRows, N - first)
-        search:update(data:narrow(1, first + 1, n), n, first)
+        search:update({ptr = set.images.ptr + first * elems}, n, first)
     end
-    local indices = search:result()
-    local found = torch.FloatTensor(k, c, h, w)
-    for i = 1, k do found[i] = data[indices[i] + 1] end
-    local nhwc = FG.to_device_nhwc(found)
-    FG.check(FG.C.fg_d2d(FG.ctx, both.ptr + k * elems, nhwc.ptr, k * elems * 4))
+    local neighbours = FG.DeviceTensor(k * elems)
+    FG.gatherImages(set.images, N, c, h, w, 1, {ptr = search.index}, k, neighbours, 0)      -- the device's own best_index
+    FG.check(FG.C.fg_d2d(FG.ctx, both.ptr + k * elems, neighbours.ptr, k * elems * 4))
     local order = {}
     for i = 1, k do order[2 * i - 1], order[2 * i] = i - 1, k + i - 1 end
     return s:grid(FG.indexTensor(order), 2 * k, k, 0, true, both)
