@@ -269,6 +269,24 @@ int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int 
     if (n == 0) return FG_OK;
     return fg_launch_gather_images(ctx, set, n_set, c, h * w, set_layout, idx, n, out, out_layout);
 }
+int fg_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                   const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    if (!set || !idx || !out || n_set < 1 || c < 1 || hs < 1 || ws < 1 || ho < 1 || wo < 1 || n < 0 || (set_layout != 0 && set_layout != 1) ||
+        (out_layout != 0 && out_layout != 1) || (fill != 0 && fill != 1))
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_images: bad argument (n_set=%lld c=%d %dx%d -> %dx%d n=%d layouts %d -> %d fill=%d)", n_set, c,
+                          hs, ws, ho, wo, n, set_layout, out_layout, fill);
+    if (!mats && (ho != hs || wo != ws))
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_images: without matrices the batch has the set's size, not %dx%d -> %dx%d", hs, ws, ho, wo);
+    // (products of two ints at a time: three could pass 2^63)
+    if ((long long)c * hs > FG_WARP_MAX_FLOATS || (long long)c * hs * ws > FG_WARP_MAX_FLOATS)
+        return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "fg_warp_images: a source image of %d x %d x %d = %.0f floats is above the %d that fit in LDS", c,
+                          hs, ws, (double)c * hs * ws, FG_WARP_MAX_FLOATS);
+    if ((long long)c * ho >= (1LL << 31) || (long long)c * ho * wo >= (1LL << 31))
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_images: an output image of %d x %d x %d floats is 2^31 floats or more", c, ho, wo);
+    if (n == 0) return FG_OK;
+    return fg_launch_warp_images(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, out, ho, wo, out_layout, fill);
+}
 int fg_rng_uniform(fg_ctx* ctx, uint64_t seed, uint64_t off, float* o, long long n, float lo, float hi) {
     NEED(ctx, ctx && o && n >= 0, "bad argument");
     return fg_launch_rng_uniform(ctx, seed, off, o, n, lo, hi);

@@ -434,6 +434,11 @@ int fg_defer_flush(fg_ctx* ctx);
 // image.scale (Torch7 `image`, bilinear): src [N][Hs][Ws][C] (nchw: [N][C][Hs][Ws]) -> dst at Hd x Wd; diff = sub_from - dst (optional)
 int fg_launch_scale_bilinear(fg_ctx*, const float* src, float* dst, int N, int C, int Hs, int Ws, int Hd, int Wd, int nchw,
                              const float* sub_from, float* diff);
+// out[j] = clamp01(gains[j] * bilinear(set[idx[j]], mats[j])) (fg_warp_images): the source image of a block lives in LDS, so
+// c * hs * ws <= FG_WARP_MAX_FLOATS (64 KB, the dynamic LDS a launch gets without an attribute change); mats / gains may be null
+#define FG_WARP_MAX_FLOATS 16384
+int fg_launch_warp_images(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                          const float* gains, int n, float* out, int ho, int wo, int out_nchw, int edge);
 int fg_launch_zero_insert2(fg_ctx*, const float* g, float* out, int B, int H, int W, int C);   // g [B][H][W][C] -> out [B][2H][2W][C]
 
 // thin convolutions (3 <-> wide channels), NHWC, stride 1, "same" pad, odd k <= 7

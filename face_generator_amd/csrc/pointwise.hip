@@ -2117,9 +2117,116 @@ __device__ __forceinline__ float fg_scale_eval(const ScaleTerm& t, F fetch) {
     if (t.div) acc = acc / t.n;
     return acc;
 }
+// fg_warp_images (include/facegen_hip.h): out[j] = clamp01(gains[j] * bilinear(set[idx[j]], affine map mats[j])), the WARP = 1
+// instances of scale_bilinear_kernel (WARP = 0 is image.scale, its body what it was).  One block per output image:
+//   - the source image (c * hs * ws <= 16384 floats) goes to LDS as it lies in the set, 16 bytes per lane where `vec` allows;
+//   - a thread owns output pixels p = tid, tid + 256, ..: the source coordinates, the range test and the four tap offsets are
+//     taken once per pixel, then every channel reads its four taps from LDS (lanes on neighbouring pixels: stride 1 in a
+//     channel-major image, stride c in a pixel-major one -- c = 3 keeps a 32-lane group on 32 banks) and writes one float:
+//     an NCHW batch gets 256 contiguous bytes per wave and channel, an NHWC one the c floats of each pixel, the wave's
+//     pixels side by side;
+//   - (y, x) of a pixel advance by the quotient and remainder of 256 by wo, taken once: no division in the loops; indices are
+//     32-bit inside an image, the image's base 64-bit.
+// Every product, sum and difference is rounded on its own, in the order the header states (no FMA contraction): a numpy fp32
+// restatement matches bit for bit.  Out of the image: a tap is 0 (fill 0: the lane reads the LDS copy of pixel 0 instead and
+// drops it, so that the four reads of a channel are in flight together); coordinates are clamped in float before the floor
+// (fill 1); the range test comes before any float-to-int conversion, so NaN, inf and huge coordinates address nothing.  Global
+// memory is read only by the copy of the image into LDS.
+template <bool SET_NCHW, bool OUT_NCHW>
+__device__ __forceinline__ void wi_image(const float* __restrict__ set, float* __restrict__ out, const int* __restrict__ idx,
+                                         const float* __restrict__ mats, const float* __restrict__ gains, long long n_set, int c, int hs,
+                                         int ws, int ho, int wo, int edge, int vec) {
+#pragma clang fp contract(off)
+    extern __shared__ float4 wi_lds[];                                      // c * hs * ws floats
+    float* img = reinterpret_cast<float*>(wi_lds);
+    const int tid = (int)threadIdx.x, j = (int)blockIdx.x;
+    const int Ps = hs * ws, Po = ho * wo, E = c * Ps, Eo = c * Po;
+    float* __restrict__ o = out + (long long)j * Eo;
+    const int i = idx[j];
+    if (i < 0 || (long long)i >= n_set) {                                   // outside the set: nothing is read, the image is NaN
+        for (int e = tid; e < Eo; e += 256) o[e] = gi_nan();
+        return;
+    }
+    const float* __restrict__ s = set + (long long)i * E;
+    if (vec) {                                                              // E % 4 == 0 and a 16-byte aligned set
+        // four loads per lane issued before the first is used.  No branch: a slot past the end of the image (the last round
+        // only) moves the lane's first slot once more, from the same source to the same place
+        for (int e0 = tid * 4; e0 < E; e0 += 4096) {
+            const int e1 = e0 + 1024 < E ? e0 + 1024 : e0, e2 = e0 + 2048 < E ? e0 + 2048 : e0, e3 = e0 + 3072 < E ? e0 + 3072 : e0;
+            const float4 v0 = *reinterpret_cast<const float4*>(s + e0), v1 = *reinterpret_cast<const float4*>(s + e1);
+            const float4 v2 = *reinterpret_cast<const float4*>(s + e2), v3 = *reinterpret_cast<const float4*>(s + e3);
+            *reinterpret_cast<float4*>(img + e0) = v0;
+            *reinterpret_cast<float4*>(img + e1) = v1;
+            *reinterpret_cast<float4*>(img + e2) = v2;
+            *reinterpret_cast<float4*>(img + e3) = v3;
+        }
+    } else {
+        for (int e0 = tid; e0 < E; e0 += 1024) {
+            const int e1 = e0 + 256 < E ? e0 + 256 : e0, e2 = e0 + 512 < E ? e0 + 512 : e0, e3 = e0 + 768 < E ? e0 + 768 : e0;
+            const float v0 = s[e0], v1 = s[e1], v2 = s[e2], v3 = s[e3];
+            img[e0] = v0;
+            img[e1] = v1;
+            img[e2] = v2;
+            img[e3] = v3;
+        }
+    }
+    float m0 = 1.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 1.f, m5 = 0.f;
+    if (mats) { const float* m = mats + 6 * (long long)j; m0 = m[0]; m1 = m[1]; m2 = m[2]; m3 = m[3]; m4 = m[4]; m5 = m[5]; }
+    const float g = gains ? gains[j] : 1.f;
+    const float wsf = (float)ws, hsf = (float)hs, xmax = (float)(ws - 1), ymax = (float)(hs - 1);
+    int y = tid / wo, x = tid - y * wo;
+    const int qy = 256 / wo, rx = 256 - qy * wo;
+    __syncthreads();
+    for (int p = tid; p < Po; p += 256) {
+        const float xf = (float)x, yf = (float)y;
+        float sx = (m0 * xf + m1 * yf) + m2;
+        float sy = (m3 * xf + m4 * yf) + m5;
+        bool inside = true;
+        if (edge) {
+            sx = fminf(fmaxf(sx, 0.f), xmax);
+            sy = fminf(fmaxf(sy, 0.f), ymax);
+        } else
+            inside = sx > -1.f && sx < wsf && sy > -1.f && sy < hsf;
+        int oa = -1, ob = -1, oc = -1, od = -1;                             // pixel offsets of the four taps, -1: outside
+        float fx = 0.f, fy = 0.f;
+        if (inside) {
+            const float x0f = floorf(sx), y0f = floorf(sy);
+            fx = sx - x0f; fy = sy - y0f;
+            const int x0 = (int)x0f, y0 = (int)y0f;                         // -1 .. ws - 1, -1 .. hs - 1
+            const bool xl = x0 >= 0, xr = x0 + 1 < ws, yt = y0 >= 0, yb = y0 + 1 < hs;
+            const int at = y0 * ws + x0;
+            if (yt && xl) oa = at;
+            if (yt && xr) ob = at + 1;
+            if (yb && xl) oc = at + ws;
+            if (yb && xr) od = at + ws + 1;
+        }
+        const int ts = SET_NCHW ? 1 : c, cs = SET_NCHW ? Ps : 1;            // strides of a pixel and of a channel in the LDS image
+        // (a tap outside the image reads the LDS copy of pixel 0 and drops it: four reads in flight per channel, no branch)
+        const int ia = (oa < 0 ? 0 : oa) * ts, ib = (ob < 0 ? 0 : ob) * ts, ic = (oc < 0 ? 0 : oc) * ts, id = (od < 0 ? 0 : od) * ts;
+        float* __restrict__ op = OUT_NCHW ? o + p : o + p * c;
+        const int os = OUT_NCHW ? Po : 1;
+        for (int ch = 0; ch < c; ++ch) {
+            const float* pl = img + ch * cs;
+            const float ra = pl[ia], rb = pl[ib], rc = pl[ic], rd = pl[id];
+            const float a = oa >= 0 ? ra : 0.f, b = ob >= 0 ? rb : 0.f, cc = oc >= 0 ? rc : 0.f, d = od >= 0 ? rd : 0.f;
+            const float top = a + (b - a) * fx, bot = cc + (d - cc) * fx;
+            float v = top + (bot - top) * fy;
+            if (gains) v = fminf(fmaxf(v * g, 0.f), 1.f);
+            op[ch * os] = v;
+        }
+        x += rx; y += qy;
+        if (x >= wo) { x -= wo; ++y; }
+    }
+}
+template <int WARP = 0, bool SET_NCHW = false, bool OUT_NCHW = false>
 __global__ __launch_bounds__(256) void scale_bilinear_kernel(const float* __restrict__ src, float* __restrict__ dst, long long total, int C, int Hs,
                                                              int Ws, int Hd, int Wd, int nchw, const float* __restrict__ sub_from,
-                                                             float* __restrict__ diff) {
+                                                             float* __restrict__ diff, const int* __restrict__ picks, const float* __restrict__ gains,
+                                                             int edge) {
+    if constexpr (WARP) {
+        // total: images of the set; sub_from: the matrices; nchw: 16-byte loads of the source image
+        wi_image<SET_NCHW, OUT_NCHW>(src, dst, picks, sub_from, gains, total, C, Hs, Ws, Hd, Wd, edge, nchw);
+    } else {
 #pragma clang fp contract(off)
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
     long long r = idx;
@@ -2137,13 +2244,30 @@ __global__ __launch_bounds__(256) void scale_bilinear_kernel(const float* __rest
     dst[idx] = v;
     if (diff) diff[idx] = sub_from[idx] - v;
     }
+    }
 }
 int fg_launch_scale_bilinear(fg_ctx* ctx, const float* src, float* dst, int N, int C, int Hs, int Ws, int Hd, int Wd, int nchw,
                              const float* sub_from, float* diff) {
     const long long total = (long long)N * C * Hd * Wd;
     if (total == 0) return FG_OK;
     hipLaunchKernelGGL(scale_bilinear_kernel, FG_GRID(total, 256), dim3(256), 0, ctx->stream, src, dst, total, C, Hs, Ws, Hd, Wd, nchw,
-                       sub_from, diff);
+                       sub_from, diff, (const int*)nullptr, (const float*)nullptr, 0);
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
+// fg_warp_images: one block per output image, the exact count (the kernel walks no grid); c * hs * ws <= FG_WARP_MAX_FLOATS, checked
+// by the entry.  One channel: the two layouts are one order, and the NCHW instance serves all four pairs
+int fg_launch_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx,
+                          const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_nchw, int edge) {
+    const int E = c * hs * ws;
+    const size_t lds = ((size_t)E * sizeof(float) + 15) & ~(size_t)15;
+    const int vec = ((size_t)set & 15) == 0 && E % 4 == 0;
+    const dim3 images((unsigned)n);
+    if (c == 1) set_nchw = out_nchw = 1;
+    if (set_nchw && out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, true, true>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge);
+    if (set_nchw && !out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, true, false>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge);
+    if (!set_nchw && out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, false, true>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge);
+    if (!set_nchw && !out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, false, false>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge);
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }

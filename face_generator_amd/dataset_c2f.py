@@ -73,12 +73,20 @@ class ResidentResult:
         return Example(self.coarse[i], self.fine[i], self.diff[i])
 
 
-def toResultResident(fineImages, coarseScale, fineScale, ctx=None):
+def toResultResident(fineImages, coarseScale, fineScale, ctx=None, augment=None):
     """toResult that leaves the epoch's set on the device: fineImages (host or device [N, C, fineScale, fineScale]) is uploaded
-    once, coarse and diff are computed once by fg_c2f_coarse_diff, and all three stay in HBM as DeviceDatasets."""
+    once, coarse and diff are computed once by fg_c2f_coarse_diff, and all three stay in HBM as DeviceDatasets.  An Augmenter
+    (augment=, or a DeviceDataset that carries one) is refused: coarse and diff are computed once from the stored fine images, and
+    a fine image under a fresh transform per batch would need both again per batch."""
     from . import ops
-    from .runtime import get_context, DeviceDataset
+    from .runtime import get_context, DeviceDataset, FgError
     ctx = ctx or get_context()
+    if isinstance(fineImages, DeviceDataset):
+        augment = augment or fineImages.augment
+        fineImages = fineImages.images
+    if augment is not None:
+        raise FgError("toResultResident: an augmented set is not supported -- coarse and diff are computed once from the stored "
+                      "fine images; augment the images before, or train adversarial.train on an augmented DeviceDataset")
     fine = torch.as_tensor(fineImages)
     if fine.dim() != 4 or fine.shape[-1] != fineScale or fine.shape[-2] != fineScale:
         raise ValueError("toResultResident: fine images must be [N, C, %d, %d]" % (fineScale, fineScale))

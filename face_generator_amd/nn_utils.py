@@ -124,7 +124,8 @@ def findClosestNeighboursOf(images, trainingSet, chunk_rows=8192, ctx=None):
             search.update(trainingSet.rows(lo, min(lo + chunk_rows, N)), lo)
         index, dist = search.result()
         found = [(int(i), float(d)) for i, d in zip(index.tolist(), dist.tolist())]
-        return found, trainingSet.gather(search.best_index, layout="nchw")
+        # (the stored images, as rows(): never a warped copy of the neighbour)
+        return found, trainingSet.gather(search.best_index, layout="nchw", augment=False)
     for lo in range(0, N, chunk_rows):
         search.update(_set_rows(trainingSet, lo, min(lo + chunk_rows, N)), lo)
     index, dist = search.result()

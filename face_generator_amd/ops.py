@@ -181,6 +181,44 @@ def scale_bilinear(x, width, height, layout="nhwc", ctx=None):
     return y
 
 
+def warp_images(images, indices, mats=None, gains=None, out_hw=None, set_layout="nchw", out_layout="nhwc", fill="constant", out=None,
+                ctx=None):
+    """out[j] = clamp01(gains[j] * bilinear(images[indices[j]], mats[j])): include/facegen_hip.h fg_warp_images.  images: device
+    [N][C][H][W] (set_layout "nchw") or [N][H][W][C]; indices: device int32 [n]; mats: device float32 [n][6] (output pixel ->
+    source pixel) or None, the identity; gains: device float32 [n] or None (gain 1, no clamp); out_hw: (ho, wo), default the set's;
+    fill: "constant" (0 outside the image) or "edge".  -> device [n][ho][wo][C] ("nhwc") or [n][C][ho][wo]."""
+    ctx = ctx or get_context()
+    layouts, fills = {"nhwc": 0, "nchw": 1}, {"constant": 0, "edge": 1}
+    if set_layout not in layouts or out_layout not in layouts or fill not in fills:
+        raise ValueError("warp_images: layouts are 'nhwc' / 'nchw', fill is 'constant' / 'edge'")
+    if images.dim() != 4 or images.dtype != torch.float32 or not images.is_contiguous():
+        raise ValueError("warp_images: images must be a contiguous float32 tensor of 4 dimensions")
+    if layouts[set_layout]:
+        N, C, H, W = images.shape
+    else:
+        N, H, W, C = images.shape
+    ho, wo = (H, W) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    if indices.dtype != torch.int32 or indices.dim() != 1 or not indices.is_contiguous():
+        raise ValueError("warp_images: indices must be a contiguous 1-d int32 tensor")
+    n = int(indices.numel())
+    for name, t, count in (("mats", mats, 6 * n), ("gains", gains, n)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != count):
+            raise ValueError("warp_images: %s must be a contiguous float32 tensor of %d elements" % (name, count))
+    shape = (n, C, ho, wo) if layouts[out_layout] else (n, ho, wo, C)
+    if out is None:
+        out = ctx.empty(*shape)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * C * ho * wo:
+        raise ValueError("warp_images: out must be a contiguous float32 tensor of %d elements" % (n * C * ho * wo))
+    for name, t in (("images", images), ("indices", indices), ("mats", mats), ("gains", gains), ("out", out)):
+        if t is not None and t.device != ctx.device:
+            raise ValueError("warp_images: %s lives on %s, the context on %s" % (name, t.device, ctx.device))
+    if n:                                   # (an empty tensor has no address to hand over)
+        ctx.check(ctx.lib.fg_warp_images(ctx.h, images.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
+                                         None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n,
+                                         out.data_ptr(), ho, wo, layouts[out_layout], fills[fill]))
+    return out.view(*shape)
+
+
 def c2f_coarse_diff(fine, coarse_scale, layout="nhwc", ctx=None):
     """dataset._toResult's arithmetic (dataset_c2f.lua:53-61) on a device batch of square images: -> (coarse, diff) with
     coarse = scale(scale(fine, cs, cs), s, s) and diff = fine - coarse.  include/facegen_hip.h fg_c2f_coarse_diff."""

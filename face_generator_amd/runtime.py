@@ -738,10 +738,11 @@ class DeviceDataset:
     dataset protocol -- size(), len(), ds[i] -> host CHW tensor (dataset.lua:66-69) -- and adds gather(): dataset[i] for a whole
     batch of indices as one launch of fg_gather_images, in the layout the steps and the nets take."""
 
-    def __init__(self, ctx, images, scale=None):
+    def __init__(self, ctx, images, scale=None, augment=None):
         """images: host or device float32 [N][C][H][W], tensor or array.  scale: side to scale every image to on the device
-        (image.scale, dataset.lua:95) when H, W differ from it."""
+        (image.scale, dataset.lua:95) when H, W differ from it.  augment: an Augmenter for gather(), see set_augment()."""
         self.ctx, self.lib = ctx, ctx.lib
+        self.set_augment(augment)
         x = torch.as_tensor(images)
         if x.dim() != 4 or x.shape[0] < 1:
             raise FgError("DeviceDataset: images must be [N][C][H][W] with N >= 1, got %s" % (tuple(x.shape),))
@@ -779,11 +780,20 @@ class DeviceDataset:
             raise IndexError("DeviceDataset.gather: index outside [0, %d)" % self.n)
         return host.to(torch.int32).to(self.ctx.device)
 
-    def gather(self, indices, layout="nhwc", out=None):
+    def set_augment(self, augment):
+        """augment: an Augmenter (every gather() then returns its images under fresh random transforms) or None"""
+        if augment is not None and not isinstance(augment, Augmenter):
+            raise FgError("DeviceDataset: augment must be a runtime.Augmenter or None")
+        self.augment = augment
+
+    def gather(self, indices, layout="nhwc", out=None, augment=True):
         """-> device [n][H][W][C] ("nhwc", what step_D / step_G and the nets take) or [n][C][H][W] ("nchw") with out[j] =
-        dataset[indices[j]]; repeated indices are legal."""
+        dataset[indices[j]]; repeated indices are legal.  With an Augmenter set (and augment=True) every image comes back under a
+        fresh random transform, at the augmenter's out_hw: one draw, one upload, one launch of fg_warp_images."""
         if layout not in ("nhwc", "nchw"):
             raise FgError("DeviceDataset.gather: layout must be 'nhwc' or 'nchw'")
+        if augment and self.augment is not None:
+            return self._gather_warped(indices, layout, out)
         idx = self.indices(indices)
         n = int(idx.numel())
         shape = (n, self.h, self.w, self.c) if layout == "nhwc" else (n, self.c, self.h, self.w)
@@ -795,3 +805,105 @@ class DeviceDataset:
             self.ctx.check(self.lib.fg_gather_images(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1,
                                                      idx.data_ptr(), n, out.data_ptr(), 0 if layout == "nhwc" else 1))
         return out.view(*shape)
+
+    def _gather_warped(self, indices, layout, out):
+        aug = self.augment
+        ho, wo = aug.out_hw
+        idx = self.indices(indices)
+        n = int(idx.numel())
+        shape = (n, ho, wo, self.c) if layout == "nhwc" else (n, self.c, ho, wo)
+        if out is None:
+            out = self.ctx.empty(*shape)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * self.c * ho * wo:
+            raise FgError("DeviceDataset.gather: out must be a contiguous float32 tensor of %d elements" % (n * self.c * ho * wo))
+        if n:
+            mats, gains = aug.draw(n, (self.h, self.w))
+            both = torch.cat([torch.from_numpy(mats).reshape(-1), torch.from_numpy(gains)]).to(self.ctx.device)     # one transfer
+            self.ctx.check(self.lib.fg_warp_images(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1, idx.data_ptr(),
+                                                   both.data_ptr(), both.data_ptr() + 24 * n, n, out.data_ptr(), ho, wo,
+                                                   0 if layout == "nhwc" else 1, aug.fill_code))
+        return out.view(*shape)
+
+
+def _minmax(v, negate):
+    """(lo, hi) as it is; a single number v: (-v, v) if negate (rotation, shear, translation) else (v, 2 - v) (zoom around 1)"""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise FgError("Augmenter: a range is (min, max)")
+        return v[0], v[1]
+    return ((-1) * v, v) if negate else (v, 1.0 - (v - 1.0))
+
+
+class Augmenter:
+    """The random transforms of dataset/generate_dataset.py (:43-48: every face flipped with p = 0.5, brightness x0.9 .. 1.1, zoom
+    0.82 .. 1.10, rotation +-8 deg, translation +-5 px, bilinear warp with black fill, written 19 times to disk before training) as
+    matrices and gains for fg_warp_images, drawn per batch: DeviceDataset(.., augment=Augmenter((32, 32))) holds the un-augmented
+    set once and hands out every image under a fresh transform.
+
+    out_hw: (height, width) of the images handed out; the set's may be larger (a margin that rotations and shifts draw from).
+    The defaults are the reference's call; its 5 px of translation belong to the 250-px picture whose 84-px crop becomes the
+    face, hence round(5 * side / 84) px here.  Angles in degrees, ranges as (min, max) or one number for +-that (zoom: v .. 2 - v).
+    The augmenter owns a random.Random(seed) -- the reference seeds with 43 -- and never touches state.S.rng: the index picks
+    of the training loops are the same stream with and without augmentation."""
+
+    def __init__(self, out_hw, hflip=True, vflip=False, scale_to_percent=(0.82, 1.10), scale_axis_equally=True, rotation_deg=8,
+                 shear_deg=0, translation_x_px=None, translation_y_px=None, brightness_change=0.1, fill="constant", seed=43):
+        import random
+        ho, wo = (int(out_hw), int(out_hw)) if isinstance(out_hw, int) else (int(out_hw[0]), int(out_hw[1]))
+        if ho < 1 or wo < 1:
+            raise FgError("Augmenter: out_hw must be positive, got %s" % (out_hw,))
+        if fill not in ("constant", "edge"):
+            raise FgError("Augmenter: fill must be 'constant' or 'edge'")
+        self.out_hw, self.fill, self.fill_code = (ho, wo), fill, 0 if fill == "constant" else 1
+        self.hflip, self.vflip, self.scale_axis_equally = bool(hflip), bool(vflip), bool(scale_axis_equally)
+        self.scale = _minmax(scale_to_percent, False)
+        if self.scale[0] <= 0:
+            raise FgError("Augmenter: scale_to_percent must be positive")
+        self.rotation, self.shear = _minmax(rotation_deg, True), _minmax(shear_deg, True)
+        self.tx = _minmax(int(round(5.0 * wo / 84.0)) if translation_x_px is None else translation_x_px, True)
+        self.ty = _minmax(int(round(5.0 * ho / 84.0)) if translation_y_px is None else translation_y_px, True)
+        self.brightness = float(brightness_change)
+        self.rng = random.Random(seed)
+
+    def draw_one(self):
+        """the random picks of one image, in this order: flip(s) (only the enabled axes), zoom (twice unless equal), rotation, shear,
+        translation x, translation y, brightness -> (hflip, vflip, zoom_x, zoom_y, rotation deg, shear deg, tx, ty, gain)"""
+        r = self.rng
+        hf = self.hflip and r.random() > 0.5
+        vf = self.vflip and r.random() > 0.5
+        zx = r.uniform(*self.scale)
+        zy = zx if self.scale_axis_equally else r.uniform(*self.scale)
+        rot, sh = r.randint(*self.rotation), r.randint(*self.shear)
+        tx, ty = r.randint(*self.tx), r.randint(*self.ty)
+        gain = r.uniform(1.0 - self.brightness, 1.0 + self.brightness)
+        return hf, vf, zx, zy, rot, sh, tx, ty, gain
+
+    def matrix(self, pick, src_hw):
+        """output pixel -> source pixel, six Python floats (float64) [m0 .. m5]: the forward map q = L (p - centre) + centre + t
+        (L: zoom, rotation and shear, t: the translation, about the centre of the output) inverted in closed form,
+        p = L^-1 (q - centre - t) + centre, moved by the set's margin, then mirrored in the source where the pick flips (the
+        reference flips the picture before it warps it).  Plain float arithmetic: a batch of 64 costs well under a millisecond."""
+        import math
+        hf, vf, zx, zy, rot, sh, tx, ty, _ = pick
+        (ho, wo), (hs, ws) = self.out_hw, src_hw
+        r, s = math.radians(rot), math.radians(sh)
+        a, b, c, d = zx * math.cos(r), 0.0 - zy * math.sin(r + s), zx * math.sin(r), zy * math.cos(r + s)
+        det = a * d - b * c
+        ia, ib, ic, id_ = d / det, (0.0 - b) / det, (0.0 - c) / det, a / det
+        cx, cy = int(wo / 2), int(ho / 2)
+        qx, qy = cx + tx, cy + ty
+        m = [ia + 0.0, ib + 0.0, cx - (ia * qx + ib * qy) + (ws - wo) / 2.0, ic + 0.0, id_ + 0.0, cy - (ic * qx + id_ * qy) + (hs - ho) / 2.0]
+        if hf:
+            m[0:3] = [0.0 - m[0], 0.0 - m[1], (ws - 1) - m[2]]
+        if vf:
+            m[3:6] = [0.0 - m[3], 0.0 - m[4], (hs - 1) - m[5]]
+        return m
+
+    def draw(self, n, src_hw):
+        """-> host float32 (mats [n][6], gains [n]) for n images of a set whose images are src_hw = (hs, ws): the matrices are
+        assembled in float64 and rounded once"""
+        import numpy as np
+        src_hw = (int(src_hw[0]), int(src_hw[1]))
+        picks = [self.draw_one() for _ in range(n)]
+        mats = np.array([self.matrix(p, src_hw) for p in picks], dtype=np.float64).reshape(n, 6)
+        return mats.astype(np.float32), np.array([p[8] for p in picks], dtype=np.float64).astype(np.float32)

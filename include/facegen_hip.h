@@ -533,6 +533,39 @@ int fg_nearest_update(fg_ctx* ctx, const float* queries, int q, const float* row
 int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int h, int w, int set_layout, const int* idx, int n,
                      float* out, int out_layout);
 
+/* ---- dataset[i] under a fresh random transform: the augmentation of dataset/generate_dataset.py (19 warped copies of every face
+ *      written to disk before training: flip, brightness, zoom, rotation, translation, bilinear warp with black fill, :43-48, :130)
+ *      as a per-batch operation on a set that lives in HBM, gather + affine resample + gain + clamp + layout change in one launch:
+ *        out[j][.][y][x] = clamp01( gains[j] * bilinear(set[idx[j]], sx, sy) ),  j = 0 .. n-1. ----
+ * set, n_set, c, idx, n, set_layout, out_layout: as fg_gather_images; the set's images are hs x ws, the batch's ho x wo (they may
+ *   differ: a set stored with a margin, 40x40, is cropped to 32x32 by the matrix alone).  All four layout pairs.
+ * mats: device float [n][6], OUTPUT pixel (column x, row y, as fp32) -> SOURCE pixel coordinates:
+ *     sx = (m0*x + m1*y) + m2        sy = (m3*x + m4*y) + m5
+ *   All coordinate arithmetic is fp32, every operation rounded on its own in exactly this order (no fused multiply-add): the
+ *   operation order of this comment is the contract, a numpy fp32 restatement matches bit for bit.  NULL: the identity for every
+ *   image (ho == hs and wo == ws required).
+ * fill 0, constant 0 (skimage warp(order=1, mode="constant", cval=0)): if !(sx > -1 && sx < ws && sy > -1 && sy < hs) -- tested in
+ *   float before any conversion to int, so NaN, inf and huge coordinates land here -- the pixel is 0 and nothing is read.
+ *   Otherwise x0 = floor(sx), fx = sx - x0, likewise y; the taps (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1) are a, b, c, d; a
+ *   tap outside the image is 0.0f and is not read, a tap inside is read even at weight 0;
+ *     top = a + (b - a)*fx,  bot = c + (d - c)*fx,  v = top + (bot - top)*fy.
+ * fill 1, edge: sx = fminf(fmaxf(sx, 0), ws - 1), likewise sy, before the floor (a NaN coordinate becomes 0); the +1 taps that fall
+ *   outside count as 0, at weight 0.
+ * gains: device float [n]; the result is fminf(fmaxf(v * gains[j], 0), 1).  NULL: gain 1 and no clamp, so that an identity matrix
+ *   reproduces fg_gather_images bit for bit (finite pixels; v = a + (b - a)*0).
+ * An idx[j] outside [0, n_set) reads nothing and gives a quiet-NaN image (0x7fc00000), as fg_gather_images; repeated indices are
+ *   legal.  Nothing outside out[0 .. n * c * ho * wo) is written; nothing outside set, idx[0 .. n), mats[0 .. 6n), gains[0 .. n) is
+ *   read.  The image's base offset is 64-bit.  Any c, hs, ws, ho, wo >= 1.
+ * n == 0: FG_OK, nothing is launched.  NULL set / idx / out, sizes < 1, n < 0, a layout or fill other than 0 / 1, mats == NULL with
+ *   differing sizes, an output image of 2^31 floats or more: FG_ERR_INVALID, nothing is launched.  c * hs * ws > 16384 floats:
+ *   FG_ERR_UNSUPPORTED, the message names the size -- a block keeps its source image in LDS, and 16384 floats are the 64 KB a launch
+ *   gets without an attribute change (3 x 64 x 64 = 12288 is the largest image of the models here).
+ * Alignment: 4 bytes are enough; the source image is read with 16-byte accesses when `set` is 16-byte aligned and c * hs * ws % 4
+ *   == 0, the rule fg_gather_images states.  One launch on the context's stream (one block per output image), no scratch, no
+ *   atomics, no synchronisation. */
+int fg_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx,
+                   const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill);
+
 /* ---- the c2f data step in front of the train closure (dataset_c2f.lua:49-61, `dataset._toResult`) ----
  * fg_scale_bilinear = image.scale(src, width, height) of the Torch7 `image` package (default mode 'bilinear'; un-vendored luarocks
  * dependency, restated in oracle/image_scale.py): width pass then height pass; per axis up-scaling interpolates with

@@ -148,6 +148,7 @@ int fg_parzen_min_dist(fg_ctx* ctx, const float* gen, const float* cond, const f
 size_t fg_nearest_workspace_bytes(int q, int n);
 int fg_nearest_update(fg_ctx* ctx, const float* queries, int q, const float* rows, int n, long long elems, long long first_index, int first, double* best_d2, int* best_index, float* best_dist, void* scratch, size_t scratch_bytes);
 int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int h, int w, int set_layout, const int* idx, int n, float* out, int out_layout);
+int fg_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill);
 int fg_scale_bilinear(fg_ctx* ctx, const float* src, float* dst, int n, int c, int hs, int ws, int hd, int wd, int layout);
 int fg_c2f_coarse_diff(fg_ctx* ctx, const float* fine, float* coarse, float* diff, float* tmp, int n, int c, int s, int cs, int layout);
 size_t fg_conv2d_workspace_bytes(int batch, int h, int w, int cin, int cout, int k, int upsample2x);
@@ -841,6 +842,20 @@ function Dataset:gather(picks, n, outLayout)
     end
     local out = M.DeviceTensor(n * self.c * self.h * self.w)
     return M.gatherImages(self.images, self.n, self.c, self.h, self.w, 1, idx, n, out, outLayout or 0), idx
+end
+-- fg_warp_images: out[j] = clamp01(gains[j] * bilinear(set[idx[j]], mats[j])), the augmentation of dataset/generate_dataset.py per batch.
+-- mats: DeviceTensor of n * 6 floats (output pixel -> source pixel, see include/facegen_hip.h) or nil, the identity; gains: DeviceTensor
+-- of n floats or nil (gain 1, no clamp); out: n images of c * ho * wo floats in outLayout; fill: 0 = black outside the image, 1 = edge
+function M.warpImages(set, nSet, c, hs, ws, setLayout, idx, mats, gains, n, out, ho, wo, outLayout, fill)
+    check(C.fg_warp_images(ctx, set.ptr, nSet, c, hs, ws, setLayout, ffi.cast('const int*', idx.ptr), mats and mats.ptr or nil,
+                           gains and gains.ptr or nil, n, out.ptr, ho, wo, outLayout, fill or 0))
+    return out
+end
+-- ds:gatherWarped(idx, n, mats, gains, out, outLayout, fill): the batch {ds[idx[1]], ...} under the transforms mats / gains, at the
+-- set's own size (a crop of a set with a margin: M.warpImages); idx: a DeviceTensor of 0-based int32 (M.indexTensor) with its count n
+function Dataset:gatherWarped(idx, n, mats, gains, out, outLayout, fill)
+    out = out or M.DeviceTensor(n * self.c * self.h * self.w)
+    return M.warpImages(self.images, self.n, self.c, self.h, self.w, 1, idx, mats, gains, n, out, self.h, self.w, outLayout or 0, fill or 0)
 end
 -- dataset._toResult (dataset_c2f.lua:49-63) with the three sets left in HBM: {fine, coarse, diff} as FG.Datasets, :size(), [i]
 local Resident = {}
