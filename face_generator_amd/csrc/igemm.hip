@@ -1934,9 +1934,11 @@ __device__ __forceinline__ void wgrad_finish_one(const WeightMap& wm, const floa
 }
 // The same reduction for a plain k x k layer (k = 3 | 5), one block per (out-channel, 128 in-channels) and ALL taps: a thread keeps one
 // running sum per tap and walks the splits two at a time -- 2 k^2 independent loads in flight (one thread per (channel pair, tap)
-// walked its S = 7 ... 51 partials four at a time: the launch was bound by memory latency x occupancy, 39 us for D's ~85 MB).  Every
-// tap's additions stay in ascending split order (bit-identical to wgrad_finish_one); the block then writes the [in-channel][tap] run
-// of the reference layout contiguously through LDS instead of one word per 36- / 100-byte stride.
+// walked its S = 7 ... 51 partials four at a time: the launch was bound by memory latency x occupancy, 39 us for D's ~85 MB).  The
+// order of a tap's additions is fixed by S alone, so the sum is deterministic: ascending split order for S < 12 (bit-identical to
+// wgrad_finish_one), four group sums added in group order for S >= 12 (fg_finish_taps_tpb below; NOT the bits of wgrad_finish_one).
+// The block then writes the [in-channel][tap] run of the reference layout contiguously through LDS instead of one word per 36- /
+// 100-byte stride.
 __host__ __device__ static inline bool fg_finish_all_taps(const WeightMap& wm) { return !wm.wino && wm.kind == 0 && (wm.k == 3 || wm.k == 5); }
 // in-channels per block: 128 (one thread each), or -- long reductions, S >= 12 -- 32 with the splits dealt to FOUR thread groups
 // (group q sums the contiguous range [q * ceil(S / 4), ...) in ascending order, the four group sums are added in group order): D's
@@ -1991,9 +1993,11 @@ __device__ __forceinline__ void wgrad_finish_taps_any(const WeightMap& wm, const
     if (wm.k == 5) wgrad_finish_taps<5>(wm, Part, S, Npad, Cpad, beta, gradW, bx, po, sh);
     else wgrad_finish_taps<3>(wm, Part, S, Npad, Cpad, beta, gradW, bx, po, sh);
 }
-// Winograd-domain partials (WeightMap::wino, wino_wgrad.hip): Part[unit][split][Npad][Cpad][pos 16].  One thread per (out, in) pair:
-// sum the splits per position, apply the signs wino_wgrad_kernel left out of A's last row (s_i s_j, s = (1, 1, 1, -1)),
-// t = G^T (dL/dU) G, and scatter the sub-kernel gradient into the reference taps -- the exact adjoint of fg_wino_subkernel:
+// Winograd-domain partials (WeightMap::wino, wino_wgrad.hip): Part[unit][split][position quad 4][Npad][Cpad][4] -- the 16 positions of a
+// channel pair as four planes of [pair][4], so that neighbouring lanes of wino_wgrad_kernel's stores and neighbouring threads of the
+// loads here are 16 bytes apart.  One thread per (out, in) pair: sum the splits per position, apply the signs wino_wgrad_kernel left
+// out of A's last row (s_i s_j, s = (1, 1, 1, -1)), t = G^T (dL/dU) G, and scatter the sub-kernel gradient into the reference taps --
+// the exact adjoint of fg_wino_subkernel:
 //   wino 1, kind 0 (3x3): taps = t;   wino 1, kind 1 (folded): tap (dy, dx) collects t_p[fold(py, dy)][fold(px, dx)] of every parity p;
 //   wino 2 (5x5): tap (3a + dy, 3b + dx) = t_(a, b)[dy][dx].
 // Threads: a block of 128 owns one out-channel and 128 in-channels of a one-unit layer, or 32 in-channels x the 4 units (parities /
@@ -2017,14 +2021,15 @@ __device__ __forceinline__ void wino_wgrad_finish_block(const WeightMap& wm, con
         float du[16];
 #pragma unroll
         for (int pos = 0; pos < 16; ++pos) du[pos] = 0.f;
-        const float4* __restrict__ b = (const float4*)(Part + ((size_t)u * S * tile + (size_t)o * Cpad + i) * 16);
+        // positions 4 q .. 4 q + 3 of split s: one float4 at b[(s * 4 + q) * tile]
+        const float4* __restrict__ b = (const float4*)Part + (size_t)u * S * tile * 4 + (size_t)o * Cpad + i;
         int s = 0;
         for (; s + 4 <= S; s += 4) {          // four splits = sixteen 16-byte loads in flight; the additions stay in split order
             float4 v[4][4];
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[e][q] = b[(size_t)(s + e) * tile * 4 + q];
+                for (int q = 0; q < 4; ++q) v[e][q] = b[((size_t)(s + e) * 4 + q) * tile];
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -2033,7 +2038,7 @@ __device__ __forceinline__ void wino_wgrad_finish_block(const WeightMap& wm, con
         for (; s < S; ++s) {
             float4 v[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = b[(size_t)s * tile * 4 + q];
+            for (int q = 0; q < 4; ++q) v[q] = b[((size_t)s * 4 + q) * tile];
 #pragma unroll
             for (int q = 0; q < 4; ++q) { du[4 * q] += v[q].x; du[4 * q + 1] += v[q].y; du[4 * q + 2] += v[q].z; du[4 * q + 3] += v[q].w; }
         }

@@ -108,16 +108,10 @@ __device__ __forceinline__ void wino_body(const WinoArgs& a) {
     const int per = (nct + a.splits - 1) / a.splits;
     const int c0 = blockIdx.y * per;
     const int NC = max(0, min(nct, c0 + per) - c0);
-
-    if (tid < 64) {
-        const int t = tile_m * 64 + tid;
-        int off = -1;
-        if (t < a.T) {
-            int b, ty, tx;
-            wn_decode(t, a, b, ty, tx);
-            off = ((b * a.Ho + a.osy * 2 * ty + a.ooy[par]) * a.Wo + a.osx * 2 * tx + a.oox[par]) * a.N;
-        }
-        rowoff[tid] = off;
+    unsigned long long* trc = nullptr;
+    if (TRACE) {
+        if (wid == 0 && a.dbg_trace) trc = a.dbg_trace + (size_t)(blockIdx.x + gridDim.x * blockIdx.y) * 128;
+        if (trc && lane == 0) trc[0] = __builtin_amdgcn_s_memtime();
     }
 
     // ---- this thread's share of the loads: (tile tl, channel pair q) of the input patch, 8 float4 of the U chunk
@@ -128,6 +122,21 @@ __device__ __forceinline__ void wino_body(const WinoArgs& a) {
     // of zeros: its loads go through a zero-length descriptor (every lane out of range = 0).
     const __amdgpu_buffer_rsrc_t zrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.U, 0, 0, 0x00020000);
     const int NCE = (NC + 1) & ~1;
+    const int uo = tid * 4;                                                      // U: float4 number tid + 256 i of the chunk image
+    const int ubase = (par * nbn + tile_n) * nct;                                // chunk images of this (parity, channel block)
+    // two register sets per operand: while (RX, UX) -- chunk ci + 1 -- is transformed / stored, (RY, UY) receives chunk ci + 2
+    f32x2 rva[16], rvb[16];
+    f32x4 rua[8], rub[8];
+#define WN_LOAD_U(ru, c)                                                                                   \
+    {                                                                                                      \
+        const int su = (ubase + (c)) * 32768;                                                              \
+        const __amdgpu_buffer_rsrc_t ur_ = (c) < c0 + NC ? ursrc : zrsrc;                                  \
+        _Pragma("unroll") for (int i = 0; i < 8; ++i) ru[i] = wn_load4(ur_, (uo + i * 1024) * 4, su);       \
+    }
+    // U of chunk 0 is requested FIRST: its addresses need only the block index and the arguments, so the tile decode and the 16
+    // bounds-checked patch offsets below run under its latency instead of in front of it
+    if (NC > 0) WN_LOAD_U(rua, c0);
+    __builtin_amdgcn_sched_barrier(0);
     int voff[16];
     int pb, py0, px0;                                   // this thread's tile: sample row base, patch origin before the group offset
     bool tvalid;
@@ -156,8 +165,6 @@ __device__ __forceinline__ void wino_body(const WinoArgs& a) {
         _Pragma("unroll") for (int p = 0; p < 16; ++p) voff[p] = (rok_[p >> 2] & cok_[p & 3]) ? rb_[p >> 2] + (p & 3) * cstep : FG_OOB; \
     }
     const int vw = ((tid & 3) >> 1) * 256 + (tid >> 2) * 4 + (tid & 1) * 2;      // V store: [pos][half][tile][4], pos = immediate
-    const int uo = tid * 4;                                                      // U: float4 number tid + 256 i of the chunk image
-    const int ubase = (par * nbn + tile_n) * nct;                                // chunk images of this (parity, channel block)
     const int a_rd = (lane >> 5) * 256 + (wm * 32 + (lane & 31)) * 4;
     const int b_rd = 8192 + (lane >> 5) * 256 + (wn * 32 + (lane & 31)) * 4;
 
@@ -170,16 +177,11 @@ __device__ __forceinline__ void wino_body(const WinoArgs& a) {
         if (++ccl == nch) { ccl = 0; ++gl; if (gl < a.KG) WN_SET_GROUP(gl); }                              \
     }
 
-    // two register sets per operand: while (RX, UX) -- chunk ci + 1 -- is transformed / stored, (RY, UY) receives chunk ci + 2
-    f32x2 rva[16], rvb[16];
-    f32x4 rua[8], rub[8];
-#define WN_LOAD(rv, ru)                                                                                    \
+#define WN_LOAD_X(rv)                                                                                      \
     {                                                                                                      \
-        const int sx = ccl * 32, su = (ubase + cl) * 32768;                                                \
-        const bool real_ = cl < c0 + NC;                                                                   \
-        const __amdgpu_buffer_rsrc_t xr_ = real_ ? xrsrc : zrsrc, ur_ = real_ ? ursrc : zrsrc;             \
+        const int sx = ccl * 32;                                                                           \
+        const __amdgpu_buffer_rsrc_t xr_ = cl < c0 + NC ? xrsrc : zrsrc;                                   \
         _Pragma("unroll") for (int p = 0; p < 16; ++p) rv[p] = wn_load2(xr_, voff[p], sx);                 \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) ru[i] = wn_load4(ur_, (uo + i * 1024) * 4, su);       \
     }
     // input transform B^T d B of this thread's patch (two channels at a time) and the stores of a whole chunk, not interleaved
     // with anything: the prologue
@@ -216,15 +218,23 @@ __device__ __forceinline__ void wino_body(const WinoArgs& a) {
         for (int r = 0; r < 16; ++r) acc[p][r] = (p == 5 && !bias_late) ? bv : 0.f;
 
     f32x4 fa[2][2], fb[2][2];       // fragment double buffer: [set][position of the pair]
-    unsigned long long* trc = nullptr;
-    if (TRACE) {
-        if (wid == 0 && a.dbg_trace) trc = a.dbg_trace + (size_t)(blockIdx.x + gridDim.x * blockIdx.y) * 128;
-        if (trc && lane == 0) trc[0] = __builtin_amdgcn_s_memtime();
-    }
     if (NC > 0) {
         // chunks 0 and 1 requested before anything waits: the second set of loads lands while the first is transformed
-        WN_LOAD(rva, rua); WN_ADVANCE();
-        WN_LOAD(rvb, rub); WN_ADVANCE();
+        WN_LOAD_X(rva); WN_ADVANCE();
+        WN_LOAD_U(rub, cl); WN_LOAD_X(rvb); WN_ADVANCE();
+    }
+    // the output rows of this block's tiles: read by the epilogue only, so filled behind the requests (the prologue's barrier
+    // orders the fill before every wave's epilogue)
+    if (tid < 64) {
+        const int t = tile_m * 64 + tid;
+        int off = -1;
+        if (t < a.T) {
+            int b, ty, tx;
+            wn_decode(t, a, b, ty, tx);
+            const int ooy4 = *(const int*)a.ooy, oox4 = *(const int*)a.oox;      // (packed bytes, as the group offsets above)
+            off = ((b * a.Ho + a.osy * 2 * ty + WN_GOFF(ooy4, par)) * a.Wo + a.osx * 2 * tx + WN_GOFF(oox4, par)) * a.N;
+        }
+        rowoff[tid] = off;
     }
     // the 256 accumulator registers are written HERE, under the latency of the requests above (left to itself hipcc sinks the
     // initialisation behind the prologue's barrier, ~3 600 cycles on every block's critical path: 720 v_accvgpr_write)
@@ -334,7 +344,8 @@ __device__ __forceinline__ void wino_body(const WinoArgs& a) {
 #undef WN_SET_GROUP
 #undef WN_GOFF
 #undef WN_ADVANCE
-#undef WN_LOAD
+#undef WN_LOAD_U
+#undef WN_LOAD_X
 #undef WN_XFORM_STORE
 #undef WN_CHUNK
 
@@ -364,7 +375,10 @@ __device__ __forceinline__ void wino_body(const WinoArgs& a) {
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            __builtin_amdgcn_sched_barrier(0);       // one accumulator row at a time: 16 reads of the accumulator file, 24 sums, 4 stores
+            // one accumulator row at a time: 16 reads of the accumulator file, 24 sums, 4 stores.  (The column pass as packed sums on
+            // pairs of tile columns was built and dropped: pairs made of elements of different accumulator tiles send whole tiles
+            // through the vector registers -- 240 spilled; 2 with each value read out as a scalar first -- DESIGN section 8)
+            __builtin_amdgcn_sched_barrier(0);
             const int r = r4 * 4 + q;
             float t0[4], t1[4];
 #pragma unroll

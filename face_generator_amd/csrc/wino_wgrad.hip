@@ -79,7 +79,11 @@ __device__ __forceinline__ void ww_body(const WinoWgradArgs& a) {
     const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.X - xShift), 0, (int)a.x_bytes + xShift, 0x00020000);
     const int chD = tn * 64 + lane, chX = tc * 64 + lane;
     const int vD = chD < a.Nd ? chD * 4 : FG_OOB, vX = chX < a.Cx ? chX * 4 : FG_OOB;
-    const int goy = a.goy[grp], gox = a.gox[grp], ooy = a.ooy[par], oox = a.oox[par];
+    // (the offsets as packed bytes: an indexed read of the kernel arguments is a scalar memory load in front of the first cursor)
+#define WW_BYTE(pk, g) ((int)(signed char)((pk) >> (8 * (g))))
+    const int goy = WW_BYTE(*(const int*)a.goy, grp), gox = WW_BYTE(*(const int*)a.gox, grp);
+    const int ooy = WW_BYTE(*(const int*)a.ooy, par), oox = WW_BYTE(*(const int*)a.oox, par);
+#undef WW_BYTE
     const int cend = c0 + NC;
 
     // store offsets: [pos][k half][channel][4]: this wave's tile pair is k = 2 wid, 2 wid + 1
@@ -302,23 +306,25 @@ __device__ __forceinline__ void ww_body(const WinoWgradArgs& a) {
 #undef WW_XFORM_STORE
 #undef WW_CHUNK
 
-    // ---- partial dL/dU' of this split: Part[pg][split][out][in][pos 16] -- the 16 positions of a channel pair are 64 contiguous bytes
-    // (four 16-byte stores per accumulator row here, four 16-byte loads per split in the finish pass).  Lane l holds column (l & 31) =
-    // in-channel; rows = out-channels
+    // ---- partial dL/dU' of this split: Part[pg][split][position quad 4][out][in][4] -- the 16 positions of a channel pair as four
+    // planes of [pair][4]: the lanes of a store are 16 bytes apart (one 512-byte run per half wave) and so are the threads of the
+    // finish pass's loads.  (With the 16 positions of a pair contiguous, lanes 64 bytes apart, this epilogue took 45 000 cycles per
+    // block: profiles/r12_wino_fixed_cost.md.)  Lane l holds column (l & 31) = in-channel; rows = out-channels
     {
-        float* outp = a.Part + (((size_t)pg * a.S + blockIdx.y) * 16) * (size_t)a.Npad * a.Cpad;
+        const int tile = a.Npad * a.Cpad;
+        float* outp = a.Part + (((size_t)pg * a.S + blockIdx.y) * 16) * (size_t)tile;
         const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc((void*)outp, 0, FG_OOB, 0x00020000);
         const int col = tc * 64 + wn * 32 + (lane & 31);
         const int row0 = tn * 64 + wm * 32 + 4 * (lane >> 5);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = row0 + (r & 3) + 8 * (r >> 2);
-            const int vo = (row * a.Cpad + col) * 64;
+            const int vo = (row * a.Cpad + col) * 16;
             __builtin_amdgcn_sched_barrier(0);           // one accumulator row at a time (16 reads of the accumulator file, 4 stores)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const f32x4 v = {acc[4 * q][r], acc[4 * q + 1][r], acc[4 * q + 2][r], acc[4 * q + 3][r]};
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), orsrc, vo, q * 16, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), orsrc, vo, q * tile * 16, 0);
             }
         }
     }
