@@ -99,6 +99,8 @@ def train(trainData):
     print("<trainer> Epoch #%d [batchSize = %d]" % (S.EPOCH, OPT["batchSize"]))
 
     resident = is_resident(trainData)            # dataset_c2f.ResidentResult: the three sets live in HBM
+    # dataset_c2f.AugmentedResult: the fine set lives in HBM, every pull is computed under fresh transforms (one launch per pull)
+    fields = callable(getattr(trainData, "gather_fields", None))
 
     def fetch(idx, field):
         if resident:
@@ -117,7 +119,9 @@ def train(trainData):
         half = thisBatchSize // 2
         for _ in range(OPT.get("D_iterations", 1)):
             idx = [S.rng.randrange(trainData.size()) for _ in range(half)]
-            if resident:
+            if fields:                                     # diff and coarse of the same warped faces: one draw, one launch
+                diff, cond_r = trainData.gather_fields(idx, ("diff", "coarse"))
+            elif resident:
                 idx = trainData.coarse.indices(idx)        # one upload serves both gathers
                 diff, cond_r = fetch(idx, "diff"), fetch(idx, "coarse")
             else:
@@ -166,14 +170,20 @@ def approxParzen(ds, nsamples, nneighbors):
     resident = is_resident(ds)
     for n in range(nsamples):
         pick = S.rng.randrange(ds.size())
-        if resident:                        # "one image nneighbors times" and the fine image: two gathers, nothing from the host
+        fine = None
+        if callable(getattr(ds, "gather_fields", None)):     # coarse and fine of ONE transform; the repeat stays on the device
+            cond, fine = ds.gather_fields([pick], ("coarse", "fine"))
+            cond = cond.repeat(nneighbors, 1, 1, 1)
+        elif resident:                      # "one image nneighbors times" and the fine image: two gathers, nothing from the host
             cond = ds.gather([pick] * nneighbors, "coarse")
         else:
             example = ds[pick]
             cond = ctx.to_device_nhwc(torch.as_tensor(example.coarse, dtype=torch.float32).unsqueeze(0).repeat(nneighbors, 1, 1, 1))
         noise = S.next_noise(ctx, nneighbors, h * w).view(nneighbors, h, w, 1)
         neighbors = G.inner.device_net.forward(G.combine_device(ctx, noise, cond), train=G.inner.train)
-        if resident:
+        if fine is not None:
+            pass                            # gathered with its coarse image above
+        elif resident:
             fine = ds.gather([pick], "fine")
         else:
             fine = ctx.to_device_nhwc(torch.as_tensor(example.fine, dtype=torch.float32).unsqueeze(0))

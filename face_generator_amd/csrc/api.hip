@@ -287,6 +287,25 @@ int fg_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs
     if (n == 0) return FG_OK;
     return fg_launch_warp_images(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, out, ho, wo, out_layout, fill);
 }
+int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    if (!set || !idx || (!fine && !coarse && !diff) || n_set < 1 || c < 1 || hs < 1 || ws < 1 || s < 1 || cs < 1 || cs > s || n < 0 ||
+        (set_layout != 0 && set_layout != 1) || (out_layout != 0 && out_layout != 1) || (fill != 0 && fill != 1))
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_c2f: bad argument (n_set=%lld c=%d %dx%d -> %dx%d, coarse %dx%d, n=%d layouts %d -> %d fill=%d%s)",
+                          n_set, c, hs, ws, s, s, cs, cs, n, set_layout, out_layout, fill, !fine && !coarse && !diff ? ", no output" : "");
+    if (!mats && (hs != s || ws != s))
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_c2f: without matrices the batch has the set's size, not %dx%d -> %dx%d", hs, ws, s, s);
+    // (products of two ints at a time: three could pass 2^63)
+    if ((long long)c * hs > FG_WARP_MAX_FLOATS || (long long)c * hs * ws > FG_WARP_MAX_FLOATS)
+        return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "fg_warp_c2f: a source image of %d x %d x %d = %.0f floats is above the %d that fit in LDS", c, hs,
+                          ws, (double)c * hs * ws, FG_WARP_MAX_FLOATS);
+    if ((long long)c * s > FG_WARP_MAX_FLOATS || (long long)c * s * s > FG_WARP_MAX_FLOATS)
+        return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "fg_warp_c2f: a fine image of %d x %d x %d = %.0f floats is above the %d that fit in LDS", c, s, s,
+                          (double)c * s * s, FG_WARP_MAX_FLOATS);
+    if (n == 0) return FG_OK;
+    return fg_launch_warp_c2f(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, s, cs, fine, coarse, diff, out_layout, fill);
+}
 int fg_rng_uniform(fg_ctx* ctx, uint64_t seed, uint64_t off, float* o, long long n, float lo, float hi) {
     NEED(ctx, ctx && o && n >= 0, "bad argument");
     return fg_launch_rng_uniform(ctx, seed, off, o, n, lo, hi);

@@ -439,6 +439,10 @@ int fg_launch_scale_bilinear(fg_ctx*, const float* src, float* dst, int N, int C
 #define FG_WARP_MAX_FLOATS 16384
 int fg_launch_warp_images(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
                           const float* gains, int n, float* out, int ho, int wo, int out_nchw, int edge);
+// fg_warp_c2f: the warp at s x s, then coarse = scale(scale(fine, cs), s) and diff = fine - coarse inside the block; fine / coarse /
+// diff may each be null (not written).  c * hs * ws and c * s * s <= FG_WARP_MAX_FLOATS: up to 135 KB of LDS, the limit raised per context
+int fg_launch_warp_c2f(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                       const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw, int edge);
 int fg_launch_zero_insert2(fg_ctx*, const float* g, float* out, int B, int H, int W, int C);   // g [B][H][W][C] -> out [B][2H][2W][C]
 
 // thin convolutions (3 <-> wide channels), NHWC, stride 1, "same" pad, odd k <= 7

@@ -2117,6 +2117,15 @@ __device__ __forceinline__ float fg_scale_eval(const ScaleTerm& t, F fetch) {
     if (t.div) acc = acc / t.n;
     return acc;
 }
+// fg_scale_eval for a plan of dst_len >= src_len (no box: i1 == i0 + 1, no division), with both taps read before either is used
+// -- a tap the plan does not have reads tap i0 once more and is dropped.  The same product(s) and the same sum: the same bits
+template <typename F>
+__device__ __forceinline__ float fg_scale_eval_up(const ScaleTerm& t, F fetch) {
+#pragma clang fp contract(off)
+    const float a = fetch(t.i0), b = fetch(t.has_last ? t.i1 : t.i0);
+    const float acc = t.w0 * a, v = t.w1 * b;
+    return t.has_last ? acc + v : acc;
+}
 // fg_warp_images (include/facegen_hip.h): out[j] = clamp01(gains[j] * bilinear(set[idx[j]], affine map mats[j])), the WARP = 1
 // instances of scale_bilinear_kernel (WARP = 0 is image.scale, its body what it was).  One block per output image:
 //   - the source image (c * hs * ws <= 16384 floats) goes to LDS as it lies in the set, 16 bytes per lane where `vec` allows;
@@ -2132,22 +2141,8 @@ __device__ __forceinline__ float fg_scale_eval(const ScaleTerm& t, F fetch) {
 // drops it, so that the four reads of a channel are in flight together); coordinates are clamped in float before the floor
 // (fill 1); the range test comes before any float-to-int conversion, so NaN, inf and huge coordinates address nothing.  Global
 // memory is read only by the copy of the image into LDS.
-template <bool SET_NCHW, bool OUT_NCHW>
-__device__ __forceinline__ void wi_image(const float* __restrict__ set, float* __restrict__ out, const int* __restrict__ idx,
-                                         const float* __restrict__ mats, const float* __restrict__ gains, long long n_set, int c, int hs,
-                                         int ws, int ho, int wo, int edge, int vec) {
-#pragma clang fp contract(off)
-    extern __shared__ float4 wi_lds[];                                      // c * hs * ws floats
-    float* img = reinterpret_cast<float*>(wi_lds);
-    const int tid = (int)threadIdx.x, j = (int)blockIdx.x;
-    const int Ps = hs * ws, Po = ho * wo, E = c * Ps, Eo = c * Po;
-    float* __restrict__ o = out + (long long)j * Eo;
-    const int i = idx[j];
-    if (i < 0 || (long long)i >= n_set) {                                   // outside the set: nothing is read, the image is NaN
-        for (int e = tid; e < Eo; e += 256) o[e] = gi_nan();
-        return;
-    }
-    const float* __restrict__ s = set + (long long)i * E;
+// the copy of one source image of E floats into LDS, as it lies in the set (wi_image, c2f_image)
+__device__ __forceinline__ void wi_load(const float* __restrict__ s, float* __restrict__ img, int E, int vec, int tid) {
     if (vec) {                                                              // E % 4 == 0 and a 16-byte aligned set
         // four loads per lane issued before the first is used.  No branch: a slot past the end of the image (the last round
         // only) moves the lane's first slot once more, from the same source to the same place
@@ -2170,6 +2165,14 @@ __device__ __forceinline__ void wi_image(const float* __restrict__ set, float* _
             img[e3] = v3;
         }
     }
+}
+// the warp of the LDS image `img` under mats[j] / gains[j]: store(p, ch, v) takes channel ch of output pixel p = y * wo + x.  Waits
+// for the block's copy of the image (one __syncthreads) before the first tap
+template <bool SET_NCHW, typename Store>
+__device__ __forceinline__ void wi_warp(const float* __restrict__ img, const float* __restrict__ mats, const float* __restrict__ gains, int j,
+                                        int c, int hs, int ws, int ho, int wo, int edge, int tid, Store store) {
+#pragma clang fp contract(off)
+    const int Ps = hs * ws, Po = ho * wo;
     float m0 = 1.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 1.f, m5 = 0.f;
     if (mats) { const float* m = mats + 6 * (long long)j; m0 = m[0]; m1 = m[1]; m2 = m[2]; m3 = m[3]; m4 = m[4]; m5 = m[5]; }
     const float g = gains ? gains[j] : 1.f;
@@ -2203,8 +2206,6 @@ __device__ __forceinline__ void wi_image(const float* __restrict__ set, float* _
         const int ts = SET_NCHW ? 1 : c, cs = SET_NCHW ? Ps : 1;            // strides of a pixel and of a channel in the LDS image
         // (a tap outside the image reads the LDS copy of pixel 0 and drops it: four reads in flight per channel, no branch)
         const int ia = (oa < 0 ? 0 : oa) * ts, ib = (ob < 0 ? 0 : ob) * ts, ic = (oc < 0 ? 0 : oc) * ts, id = (od < 0 ? 0 : od) * ts;
-        float* __restrict__ op = OUT_NCHW ? o + p : o + p * c;
-        const int os = OUT_NCHW ? Po : 1;
         for (int ch = 0; ch < c; ++ch) {
             const float* pl = img + ch * cs;
             const float ra = pl[ia], rb = pl[ib], rc = pl[ic], rd = pl[id];
@@ -2212,18 +2213,118 @@ __device__ __forceinline__ void wi_image(const float* __restrict__ set, float* _
             const float top = a + (b - a) * fx, bot = cc + (d - cc) * fx;
             float v = top + (bot - top) * fy;
             if (gains) v = fminf(fmaxf(v * g, 0.f), 1.f);
-            op[ch * os] = v;
+            store(p, ch, v);
         }
         x += rx; y += qy;
         if (x >= wo) { x -= wo; ++y; }
+    }
+}
+template <bool SET_NCHW, bool OUT_NCHW>
+__device__ __forceinline__ void wi_image(const float* __restrict__ set, float* __restrict__ out, const int* __restrict__ idx,
+                                         const float* __restrict__ mats, const float* __restrict__ gains, long long n_set, int c, int hs,
+                                         int ws, int ho, int wo, int edge, int vec) {
+    extern __shared__ float4 wi_lds[];                                      // c * hs * ws floats
+    float* img = reinterpret_cast<float*>(wi_lds);
+    const int tid = (int)threadIdx.x, j = (int)blockIdx.x;
+    const int Po = ho * wo, E = c * hs * ws, Eo = c * Po;
+    float* __restrict__ o = out + (long long)j * Eo;
+    const int i = idx[j];
+    if (i < 0 || (long long)i >= n_set) {                                   // outside the set: nothing is read, the image is NaN
+        for (int e = tid; e < Eo; e += 256) o[e] = gi_nan();
+        return;
+    }
+    wi_load(set + (long long)i * E, img, E, vec, tid);
+    wi_warp<SET_NCHW>(img, mats, gains, j, c, hs, ws, ho, wo, edge, tid,
+                      [&](int p, int ch, float v) { o[OUT_NCHW ? ch * Po + p : p * c + ch] = v; });
+}
+// fg_warp_c2f (include/facegen_hip.h), the WARP = 2 instances of scale_bilinear_kernel: fg_warp_images at s x s followed by
+// fg_c2f_coarse_diff, one block per image, nothing but the requested outputs leaves the block.  LDS holds two images: A, the source
+// image (wi_load), and B, the warped fine image (wi_warp with a store into LDS, channel-major).  The source is dead after the
+// warp: A then takes the cs x cs image, scale(fine, cs, cs), and the last pass evaluates scale(A, s, s) per output element, reads
+// its fine value from B and writes coarse, diff = fine - coarse and fine.  Both scale passes are the nested width-then-height
+// evaluation of scale_bilinear_kernel's WARP = 0 body (fg_scale_plan / fg_scale_eval per output element), so every float is the
+// one the two entries give through HBM.  The plans depend on one coordinate and the images are square: the s + cs of them are taken
+// once per block into a third region T (no division per pixel).  A block is alone on its CU (up to 135 KB of LDS) with one wave per
+// SIMD, so nothing hides an LDS round trip: the last pass, the longest, reads its four taps together (fg_scale_eval_up).  Lanes walk
+// neighbouring pixels of one channel plane: stride 1 in the warp's stores and the last pass, stride s / cs (2 at 64 -> 32: two
+// lanes per bank) in the down pass.
+template <bool SET_NCHW, bool OUT_NCHW>
+__device__ __forceinline__ void c2f_image(const float* __restrict__ set, float* __restrict__ fine, float* __restrict__ coarse,
+                                          float* __restrict__ diff, const int* __restrict__ idx, const float* __restrict__ mats,
+                                          const float* __restrict__ gains, long long n_set, int c, int hs, int ws, int s, int cs, int edge,
+                                          int vec) {
+#pragma clang fp contract(off)
+    extern __shared__ float4 wi_lds[];                                      // A: max(c * hs * ws, c * cs * cs) floats, B: c * s * s, T
+    const int tid = (int)threadIdx.x, j = (int)blockIdx.x;
+    const int Po = s * s, Pc = cs * cs, E = c * hs * ws, Eo = c * Po, Ec = c * Pc;
+    float* A = reinterpret_cast<float*>(wi_lds);
+    float* B = A + (((E > Ec ? E : Ec) + 3) & ~3);
+    ScaleTerm* T = reinterpret_cast<ScaleTerm*>(B + Eo);                    // s plans of cs -> s, then cs plans of s -> cs
+    const long long base = (long long)j * Eo;
+    if (fine) fine += base;
+    if (coarse) coarse += base;
+    if (diff) diff += base;
+    const int i = idx[j];
+    if (i < 0 || (long long)i >= n_set) {                                   // outside the set: nothing is read, every requested image is NaN
+        for (int e = tid; e < Eo; e += 256) {
+            if (fine) fine[e] = gi_nan();
+            if (coarse) coarse[e] = gi_nan();
+            if (diff) diff[e] = gi_nan();
+        }
+        return;
+    }
+    wi_load(set + (long long)i * E, A, E, vec, tid);
+    // the images are square: one plan per coordinate and direction, taken once per block (the passes read them from LDS instead
+    // of dividing per pixel); visible behind the barrier inside wi_warp
+    for (int k = tid; k < s + cs; k += 256) T[k] = k < s ? fg_scale_plan(cs, s, k) : fg_scale_plan(s, cs, k - s);
+    wi_warp<SET_NCHW>(A, mats, gains, j, c, hs, ws, s, s, edge, tid, [&](int p, int ch, float v) { B[ch * Po + p] = v; });
+    __syncthreads();                                                        // B is complete, A is free
+    {
+        int y = tid / cs, x = tid - y * cs;
+        const int qy = 256 / cs, rx = 256 - qy * cs;
+        for (int p = tid; p < Pc; p += 256) {
+            const ScaleTerm th = T[s + x], tv = T[s + y];
+            for (int ch = 0; ch < c; ++ch) {
+                const float* plane = B + ch * Po;
+                A[ch * Pc + p] = fg_scale_eval(tv, [&](int r) {
+                    const float* row = plane + r * s;
+                    return fg_scale_eval(th, [&](int q) { return row[q]; });
+                });
+            }
+            x += rx; y += qy;
+            if (x >= cs) { x -= cs; ++y; }
+        }
+    }
+    __syncthreads();
+    int y = tid / s, x = tid - y * s;
+    const int qy = 256 / s, rx = 256 - qy * s;
+    for (int p = tid; p < Po; p += 256) {
+        const ScaleTerm th = T[x], tv = T[y];
+        for (int ch = 0; ch < c; ++ch) {
+            const float* plane = A + ch * Pc;
+            const float v = fg_scale_eval_up(tv, [&](int r) {
+                const float* row = plane + r * cs;
+                return fg_scale_eval_up(th, [&](int q) { return row[q]; });
+            });
+            const float f = B[ch * Po + p];
+            const int o = OUT_NCHW ? ch * Po + p : p * c + ch;
+            if (coarse) coarse[o] = v;
+            if (diff) diff[o] = f - v;
+            if (fine) fine[o] = f;
+        }
+        x += rx; y += qy;
+        if (x >= s) { x -= s; ++y; }
     }
 }
 template <int WARP = 0, bool SET_NCHW = false, bool OUT_NCHW = false>
 __global__ __launch_bounds__(256) void scale_bilinear_kernel(const float* __restrict__ src, float* __restrict__ dst, long long total, int C, int Hs,
                                                              int Ws, int Hd, int Wd, int nchw, const float* __restrict__ sub_from,
                                                              float* __restrict__ diff, const int* __restrict__ picks, const float* __restrict__ gains,
-                                                             int edge) {
-    if constexpr (WARP) {
+                                                             int edge, float* __restrict__ coarse) {
+    if constexpr (WARP == 2) {
+        // as WARP = 1, with dst: fine, Hd: s, Wd: cs; coarse is used by these instances alone
+        c2f_image<SET_NCHW, OUT_NCHW>(src, dst, coarse, diff, picks, sub_from, gains, total, C, Hs, Ws, Hd, Wd, edge, nchw);
+    } else if constexpr (WARP == 1) {
         // total: images of the set; sub_from: the matrices; nchw: 16-byte loads of the source image
         wi_image<SET_NCHW, OUT_NCHW>(src, dst, picks, sub_from, gains, total, C, Hs, Ws, Hd, Wd, edge, nchw);
     } else {
@@ -2251,7 +2352,7 @@ int fg_launch_scale_bilinear(fg_ctx* ctx, const float* src, float* dst, int N, i
     const long long total = (long long)N * C * Hd * Wd;
     if (total == 0) return FG_OK;
     hipLaunchKernelGGL(scale_bilinear_kernel, FG_GRID(total, 256), dim3(256), 0, ctx->stream, src, dst, total, C, Hs, Ws, Hd, Wd, nchw,
-                       sub_from, diff, (const int*)nullptr, (const float*)nullptr, 0);
+                       sub_from, diff, (const int*)nullptr, (const float*)nullptr, 0, (float*)nullptr);
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }
@@ -2264,10 +2365,37 @@ int fg_launch_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c,
     const int vec = ((size_t)set & 15) == 0 && E % 4 == 0;
     const dim3 images((unsigned)n);
     if (c == 1) set_nchw = out_nchw = 1;
-    if (set_nchw && out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, true, true>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge);
-    if (set_nchw && !out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, true, false>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge);
-    if (!set_nchw && out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, false, true>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge);
-    if (!set_nchw && !out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, false, false>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge);
+    if (set_nchw && out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, true, true>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge, (float*)nullptr);
+    if (set_nchw && !out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, true, false>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge, (float*)nullptr);
+    if (!set_nchw && out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, false, true>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge, (float*)nullptr);
+    if (!set_nchw && !out_nchw) hipLaunchKernelGGL((scale_bilinear_kernel<1, false, false>), images, dim3(256), lds, ctx->stream, set, out, n_set, c, hs, ws, ho, wo, vec, mats, (float*)nullptr, idx, gains, edge, (float*)nullptr);
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
+// fg_warp_c2f: one block per image, the exact count.  LDS: the source image (or the cs x cs one where that is larger), the fine
+// image and the s + cs scale plans: up to 2 * FG_WARP_MAX_FLOATS floats and 2 * 128 plans (c * s * s <= 16384: s <= 128) = 135 KB of
+// the CU's 160 KB: the limit of each instance is raised once per context
+int fg_launch_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                       const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw, int edge) {
+    const int E = c * hs * ws, Ec = c * cs * cs;
+    const size_t lds = (((size_t)(((E > Ec ? E : Ec) + 3) & ~3) + (size_t)c * s * s) * sizeof(float) + (size_t)(s + cs) * sizeof(ScaleTerm) + 15) & ~(size_t)15;
+    const int vec = ((size_t)set & 15) == 0 && E % 4 == 0;
+    const dim3 images((unsigned)n);
+    if (c == 1) set_nchw = out_nchw = 1;
+#define C2F(SN, ON)                                                                                                              \
+    if ((set_nchw != 0) == SN && (out_nchw != 0) == ON) {                                                                        \
+        static char attr_key;                                                                                                    \
+        if (fg_attr_first(ctx, &attr_key))                                                                                       \
+            FG_HIP(ctx, hipFuncSetAttribute((const void*)scale_bilinear_kernel<2, SN, ON>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                            (int)(2 * FG_WARP_MAX_FLOATS * sizeof(float) + 2 * 128 * sizeof(ScaleTerm))));       \
+        hipLaunchKernelGGL((scale_bilinear_kernel<2, SN, ON>), images, dim3(256), lds, ctx->stream, set, fine, n_set, c, hs, ws, s, cs, vec, \
+                           mats, diff, idx, gains, edge, coarse);                                                                \
+    }
+    C2F(true, true)
+    C2F(true, false)
+    C2F(false, true)
+    C2F(false, false)
+#undef C2F
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }

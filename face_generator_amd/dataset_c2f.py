@@ -86,13 +86,95 @@ def toResultResident(fineImages, coarseScale, fineScale, ctx=None, augment=None)
         fineImages = fineImages.images
     if augment is not None:
         raise FgError("toResultResident: an augmented set is not supported -- coarse and diff are computed once from the stored "
-                      "fine images; augment the images before, or train adversarial.train on an augmented DeviceDataset")
+                      "fine images; toResultAugmented computes them per batch from augmented images")
     fine = torch.as_tensor(fineImages)
     if fine.dim() != 4 or fine.shape[-1] != fineScale or fine.shape[-2] != fineScale:
         raise ValueError("toResultResident: fine images must be [N, C, %d, %d]" % (fineScale, fineScale))
     fine = DeviceDataset(ctx, fine)
     coarse, diff = ops.c2f_coarse_diff(fine.images, coarseScale, layout="nchw", ctx=ctx)
     return ResidentResult(fine, DeviceDataset(ctx, coarse), DeviceDataset(ctx, diff))
+
+
+FIELDS = ("fine", "coarse", "diff")
+
+
+class AugmentedResult:
+    """Result for training on freshly augmented faces: only the un-augmented fine set lives in HBM (a DeviceDataset without an
+    augmenter, its images fineScale x fineScale or larger by a margin), and every pull computes the example of each picked face
+    under a fresh random transform: warp to fineScale, scale down to coarseScale and back up, subtract, in one launch of
+    fg_warp_c2f.  gather_fields() hands out several fields of the SAME transforms (the real half of a D iteration needs diff and
+    coarse of one warped face); gather() is the one-field form, so the loops that feed a ResidentResult feed this class too."""
+
+    def __init__(self, fine, coarseScale, fineScale, augment):
+        from .runtime import Augmenter, DeviceDataset, FgError
+        if not isinstance(fine, DeviceDataset) or fine.augment is not None:
+            raise FgError("AugmentedResult: the set must be a DeviceDataset without an augmenter (the result holds the augmenter)")
+        if not isinstance(augment, Augmenter):
+            raise FgError("AugmentedResult: augment must be a runtime.Augmenter")
+        self.coarseScale, self.fineScale = int(coarseScale), int(fineScale)
+        if tuple(augment.out_hw) != (self.fineScale, self.fineScale):
+            raise FgError("AugmentedResult: the augmenter hands out %dx%d images, the fine scale is %d" % (augment.out_hw + (self.fineScale,)))
+        if not 1 <= self.coarseScale <= self.fineScale:
+            raise FgError("AugmentedResult: coarse scale %d outside 1 .. %d" % (self.coarseScale, self.fineScale))
+        self.set, self.augment, self.ctx = fine, augment, fine.ctx
+
+    def size(self):
+        return self.set.size()
+
+    def __len__(self):
+        return self.size()
+
+    def indices(self, indices):
+        """host indices (range-checked, one upload) or a device int32 tensor -> device int32 [n], as DeviceDataset.indices"""
+        return self.set.indices(indices)
+
+    def gather_fields(self, indices, fields, layout="nhwc"):
+        """-> a tuple of device tensors [n][S][S][C] ("nhwc") or [n][C][S][S] ("nchw") in the order of `fields`, a subset of
+        ("fine", "coarse", "diff"): field f of dataset[indices[j]] under transform j.  One Augmenter.draw of n transforms shared
+        by all fields, one upload, one launch."""
+        from . import ops
+        from .runtime import FgError
+        if layout not in ("nhwc", "nchw"):
+            raise FgError("AugmentedResult.gather_fields: layout must be 'nhwc' or 'nchw'")
+        fields = tuple(fields)
+        if not fields or len(set(fields)) != len(fields) or any(f not in FIELDS for f in fields):
+            raise FgError("AugmentedResult.gather_fields: fields must be a non-empty subset of %r, got %r" % (FIELDS, fields))
+        idx = self.indices(indices)
+        n, ds, s = int(idx.numel()), self.set, self.fineScale
+        if not n:
+            shape = (0, s, s, ds.c) if layout == "nhwc" else (0, ds.c, s, s)
+            return tuple(self.ctx.empty(*shape) for _ in fields)
+        mats, gains = self.augment.draw(n, (ds.h, ds.w))
+        both = torch.cat([torch.from_numpy(mats).reshape(-1), torch.from_numpy(gains)]).to(self.ctx.device)         # one transfer
+        return ops.warp_c2f(ds.images, idx, s, self.coarseScale, mats=both[:6 * n], gains=both[6 * n:], fields=fields, set_layout="nchw",
+                            out_layout=layout, fill=self.augment.fill, ctx=self.ctx)
+
+    def gather(self, indices, field, layout="nhwc"):
+        return self.gather_fields(indices, (field,), layout=layout)[0]
+
+    def __getitem__(self, i):
+        """Example(coarse, fine, diff) as host CHW tensors, all three under one fresh transform"""
+        i = int(i)
+        if i < 0 or i >= self.size():
+            raise IndexError("AugmentedResult: index %d outside [0, %d)" % (i, self.size()))
+        coarse, fine, diff = self.gather_fields([i], ("coarse", "fine", "diff"), layout="nchw")
+        return Example(coarse[0].cpu(), fine[0].cpu(), diff[0].cpu())
+
+
+def toResultAugmented(fineImages, coarseScale, fineScale, augment, ctx=None):
+    """toResult for training on freshly augmented faces: fineImages (host or device [N, C, H, W] with H, W >= fineScale, or a
+    DeviceDataset without an augmenter) is uploaded once and stays un-augmented in HBM; `augment`, an Augmenter whose out_hw is
+    (fineScale, fineScale), draws the transforms of every pull -> AugmentedResult."""
+    from .runtime import get_context, DeviceDataset, FgError
+    ctx = ctx or get_context()
+    if not isinstance(fineImages, DeviceDataset):
+        fine = torch.as_tensor(fineImages)
+        if fine.dim() != 4 or fine.shape[-1] < fineScale or fine.shape[-2] < fineScale:
+            raise ValueError("toResultAugmented: fine images must be [N, C, H, W] with H, W >= %d" % fineScale)
+        fineImages = DeviceDataset(ctx, fine)
+    elif fineImages.augment is not None:
+        raise FgError("toResultAugmented: hand the Augmenter over as augment=, not on the DeviceDataset")
+    return AugmentedResult(fineImages, coarseScale, fineScale, augment)
 
 
 def toResultDevice(fine_nhwc, coarseScale, ctx=None):

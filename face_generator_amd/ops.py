@@ -219,6 +219,46 @@ def warp_images(images, indices, mats=None, gains=None, out_hw=None, set_layout=
     return out.view(*shape)
 
 
+def warp_c2f(images, indices, fine_scale, coarse_scale, mats=None, gains=None, fields=("fine", "coarse", "diff"), set_layout="nchw",
+             out_layout="nhwc", fill="constant", ctx=None):
+    """The c2f example of images[indices[j]] under mats[j] / gains[j] in one launch: include/facegen_hip.h fg_warp_c2f.  With F =
+    warp_images(.., out_hw=(fine_scale, fine_scale)): fine = F, coarse = scale(scale(F, coarse_scale), fine_scale), diff = F -
+    coarse.  images, indices, mats, gains, the layouts and fill as warp_images; fields: the outputs wanted, a subset of ("fine",
+    "coarse", "diff") without repeats -> a tuple of device tensors [n][s][s][C] ("nhwc") or [n][C][s][s] in the order of fields;
+    what is not asked for is not written."""
+    ctx = ctx or get_context()
+    layouts, fills = {"nhwc": 0, "nchw": 1}, {"constant": 0, "edge": 1}
+    if set_layout not in layouts or out_layout not in layouts or fill not in fills:
+        raise ValueError("warp_c2f: layouts are 'nhwc' / 'nchw', fill is 'constant' / 'edge'")
+    fields = tuple(fields)
+    if not fields or len(set(fields)) != len(fields) or any(f not in ("fine", "coarse", "diff") for f in fields):
+        raise ValueError("warp_c2f: fields must be a non-empty subset of ('fine', 'coarse', 'diff'), got %r" % (fields,))
+    if images.dim() != 4 or images.dtype != torch.float32 or not images.is_contiguous():
+        raise ValueError("warp_c2f: images must be a contiguous float32 tensor of 4 dimensions")
+    if layouts[set_layout]:
+        N, C, H, W = images.shape
+    else:
+        N, H, W, C = images.shape
+    s, cs = int(fine_scale), int(coarse_scale)
+    if indices.dtype != torch.int32 or indices.dim() != 1 or not indices.is_contiguous():
+        raise ValueError("warp_c2f: indices must be a contiguous 1-d int32 tensor")
+    n = int(indices.numel())
+    for name, t, count in (("mats", mats, 6 * n), ("gains", gains, n)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != count):
+            raise ValueError("warp_c2f: %s must be a contiguous float32 tensor of %d elements" % (name, count))
+    for name, t in (("images", images), ("indices", indices), ("mats", mats), ("gains", gains)):
+        if t is not None and t.device != ctx.device:
+            raise ValueError("warp_c2f: %s lives on %s, the context on %s" % (name, t.device, ctx.device))
+    shape = (n, C, s, s) if layouts[out_layout] else (n, s, s, C)
+    out = {f: ctx.empty(*shape) for f in fields}
+    P = lambda f: out[f].data_ptr() if f in out else None
+    if n:                                   # (an empty tensor has no address to hand over)
+        ctx.check(ctx.lib.fg_warp_c2f(ctx.h, images.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
+                                      None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n, s, cs,
+                                      P("fine"), P("coarse"), P("diff"), layouts[out_layout], fills[fill]))
+    return tuple(out[f] for f in fields)
+
+
 def c2f_coarse_diff(fine, coarse_scale, layout="nhwc", ctx=None):
     """dataset._toResult's arithmetic (dataset_c2f.lua:53-61) on a device batch of square images: -> (coarse, diff) with
     coarse = scale(scale(fine, cs, cs), s, s) and diff = fine - coarse.  include/facegen_hip.h fg_c2f_coarse_diff."""

@@ -566,6 +566,32 @@ int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int 
 int fg_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx,
                    const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill);
 
+/* ---- the coarse-to-fine example under a fresh random transform (dataset_c2f.lua:49-61 applied to an augmented face): gather +
+ *      warp + scale down + scale up + subtract in one launch.  With
+ *        F = fg_warp_images(set, .., idx, mats, gains, n, F, s, s, out_layout, fill)
+ *      the entry gives  fine = F,  coarse = image.scale(image.scale(F, cs, cs), s, s),  diff = F - coarse:  every written float equals,
+ *      bit for bit, what fg_warp_images followed by fg_c2f_coarse_diff on its output gives (finite source pixels, indices inside
+ *      the set). ----
+ * set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, out_layout, fill: as fg_warp_images; the batch's images are s x s, the
+ *   coarse side is cs <= s.  mats == NULL is the identity (hs == ws == s required), gains == NULL gain 1 without the clamp.
+ * fine, coarse, diff: each n images of c x s x s device floats in out_layout, or NULL: not wanted, nothing is written for it.  At
+ *   least one is non-NULL.  All four layout pairs.
+ * An idx[j] outside [0, n_set) reads nothing of `set` and fills image j of every requested output with quiet NaN (0x7fc00000) --
+ *   a contract of its own: NaN - NaN has no pinned payload, so the composition does not define this case.
+ * Nothing outside the requested outputs is written; nothing outside set, idx[0 .. n), mats[0 .. 6n), gains[0 .. n) is read.  The
+ *   image's base offset is 64-bit.  No scratch argument, no atomics, no synchronisation: one launch on the context's stream, one
+ *   block per image; the source image, the fine image and the cs x cs image live in LDS, the intermediate batches of the
+ *   composition never reach HBM.
+ * n == 0: FG_OK, nothing is launched.  NULL ctx / set / idx, all three outputs NULL, a size < 1, n < 0, a layout or fill other than
+ *   0 / 1, cs > s, mats == NULL with differing sizes: FG_ERR_INVALID, nothing is launched.  c * hs * ws > 16384 or c * s * s > 16384
+ *   floats: FG_ERR_UNSUPPORTED, the message names the size and the limit (two images of up to 64 KB -- the small one takes the
+ *   source's place -- share the 160 KB of LDS of a compute unit).
+ * Alignment: 4 bytes are enough; the source image is read with 16-byte accesses when `set` is 16-byte aligned and c * hs * ws % 4
+ *   == 0, the rule fg_gather_images states; the outputs are written 4 bytes at a time. */
+int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx,
+                const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout,
+                int fill);
+
 /* ---- the c2f data step in front of the train closure (dataset_c2f.lua:49-61, `dataset._toResult`) ----
  * fg_scale_bilinear = image.scale(src, width, height) of the Torch7 `image` package (default mode 'bilinear'; un-vendored luarocks
  * dependency, restated in oracle/image_scale.py): width pass then height pass; per axis up-scaling interpolates with

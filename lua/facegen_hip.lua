@@ -149,6 +149,7 @@ size_t fg_nearest_workspace_bytes(int q, int n);
 int fg_nearest_update(fg_ctx* ctx, const float* queries, int q, const float* rows, int n, long long elems, long long first_index, int first, double* best_d2, int* best_index, float* best_dist, void* scratch, size_t scratch_bytes);
 int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int h, int w, int set_layout, const int* idx, int n, float* out, int out_layout);
 int fg_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill);
+int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill);
 int fg_scale_bilinear(fg_ctx* ctx, const float* src, float* dst, int n, int c, int hs, int ws, int hd, int wd, int layout);
 int fg_c2f_coarse_diff(fg_ctx* ctx, const float* fine, float* coarse, float* diff, float* tmp, int n, int c, int s, int cs, int layout);
 size_t fg_conv2d_workspace_bytes(int batch, int h, int w, int cin, int cout, int k, int upsample2x);
@@ -867,6 +868,51 @@ function Resident:size() return self.fine:size() end
 function M.residentResult(fineImages, coarseScale)
     local coarse, diff = M.coarseDiff(fineImages, coarseScale)
     return setmetatable({fine = M.Dataset(fineImages), coarse = M.Dataset(coarse), diff = M.Dataset(diff)}, Resident)
+end
+-- fg_warp_c2f: the c2f example of {ds[idx[1]], ...} under the transforms mats / gains in one launch: the warp to s x s, coarse =
+-- scale(scale(fine, cs, cs), s, s), diff = fine - coarse.  fine / coarse / diff: DeviceTensors of n * c * s * s floats in outLayout, or
+-- nil: not wanted, not written (at least one is given); idx, mats, gains, fill as ds:gatherWarped.  Returns fine, coarse, diff
+function Dataset:gatherWarpedC2F(idx, n, mats, gains, s, cs, fine, coarse, diff, outLayout, fill)
+    check(C.fg_warp_c2f(ctx, self.images.ptr, self.n, self.c, self.h, self.w, 1, ffi.cast('const int*', idx.ptr), mats and mats.ptr or nil,
+                        gains and gains.ptr or nil, n, s, cs, fine and fine.ptr or nil, coarse and coarse.ptr or nil, diff and diff.ptr or nil,
+                        outLayout or 0, fill or 0))
+    return fine, coarse, diff
+end
+-- dataset._toResult for training on freshly augmented faces: only the un-augmented fine set lives in HBM (fineImages may be larger than
+-- fineScale, a margin), every pull computes its fields under the transforms draw(n, hs, ws) -> mats, gains hands out (DeviceTensors of
+-- n * 6 and n floats, output pixel -> source pixel; nil, nil: the identity, for a set stored at fineScale).
+-- r:gatherFields(picks, {'diff', 'coarse'}) -> the fields in that order, all under ONE draw; picks as ds:gather takes them
+local Augmented = {}
+Augmented.__index = Augmented
+function Augmented:size() return self.set:size() end
+function Augmented:gatherFields(picks, fields, n, outLayout)
+    local idx = picks
+    if not picks.ptr then
+        n = #picks
+        local zero = {}
+        for i = 1, n do
+            assert(picks[i] >= 1 and picks[i] <= self.set.n, 'FG.augmentedResult:gatherFields: index out of range')
+            zero[i] = picks[i] - 1
+        end
+        idx = M.indexTensor(zero)
+    end
+    local s, out = self.fineScale, {}
+    for _, f in ipairs(fields) do
+        assert((f == 'fine' or f == 'coarse' or f == 'diff') and not out[f], 'FG.augmentedResult:gatherFields: fine / coarse / diff, once each')
+        out[f] = M.DeviceTensor(n * self.set.c * s * s)
+    end
+    local mats, gains = self.draw(n, self.set.h, self.set.w)
+    self.set:gatherWarpedC2F(idx, n, mats, gains, s, self.coarseScale, out.fine, out.coarse, out.diff, outLayout or 0, self.fill)
+    local res = {}
+    for i, f in ipairs(fields) do res[i] = out[f] end
+    return unpack(res)
+end
+function Augmented:gather(picks, field, n, outLayout) return (self:gatherFields(picks, {field}, n, outLayout)) end
+function M.augmentedResult(fineImages, coarseScale, fineScale, draw, fill)
+    assert(type(draw) == 'function', 'FG.augmentedResult: draw(n, hs, ws) -> mats, gains')
+    assert(coarseScale >= 1 and coarseScale <= fineScale, 'FG.augmentedResult: 1 <= coarseScale <= fineScale')
+    local set = M.isDataset(fineImages) and fineImages or M.Dataset(fineImages)
+    return setmetatable({set = set, coarseScale = coarseScale, fineScale = fineScale, draw = draw, fill = fill or 0}, Augmented)
 end
 
 return M
