@@ -984,6 +984,7 @@ static int launch_igemm_ws6(fg_ctx* ctx, const IgemmArgs& a, int P) {
 // fp32 rows -> split planes.  One thread per 8 consecutive channels (half a 16-channel plane row).
 __device__ __forceinline__ unsigned fg_bf16_rn(float v) {
     unsigned u = __float_as_uint(v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x0040u;      // NaN: quiet it, never let the rounding carry wrap it to +-0
     u += 0x7fffu + ((u >> 16) & 1u);
     return u >> 16;
 }

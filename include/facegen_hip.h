@@ -43,9 +43,20 @@ enum {
 /* Arithmetic of the large convolution contractions (forward / data-gradient of layers that fill the chip with 256x128
  * tiles).  mode 0 (default): native fp32 MFMA (v_mfma_f32_32x32x2_f32).  mode 6: fp32 emulated on the bf16 matrix pipe --
  * operands split exactly into three bf16 planes, six exact plane products accumulated in fp32 (dropped terms <= 2^-24
- * relative); measured more accurate than mode 0 against fp64 and ~1.7x faster.  Domain: finite operands below 2^127 in
- * magnitude (an infinity, or a value that rounds to the bf16 infinity, splits into inf - inf = NaN where mode 0 would
- * propagate inf); operands below 2^-110 lose their low plane to underflow (relative error up to 2^-16 on those).  Replaces nothing in the reference (its
+ * relative); measured more accurate than mode 0 against fp64 and ~1.7x faster.
+ * Value domain (pinned by tests/test_gpu_value_domain.py, derived in tests/VALUE_DOMAIN.md):
+ *   mode 0 (fp32 MFMA, thin and gemv kernels): all of fp32.  Subnormal operands and results are exact, nothing is flushed;
+ *     infinities and NaNs propagate as IEEE 754 has it (0 * inf = NaN).
+ *   mode 6: exact split for 2^-110 <= |x| <= 0x7f7f0000 (3.3895e38, the largest value whose high plane is finite).  Above
+ *     that (from 0x7f7f8000 on, infinities included) the high plane rounds to the bf16 infinity and the operand splits into
+ *     (inf, -inf, NaN): the result is NaN where mode 0 would give a finite value or inf.  A NaN operand stays a NaN in all three
+ *     planes, whatever its payload.  Below 2^-110 the planes are bf16 subnormals, which the matrix pipe honours (measured on
+ *     gfx950: no flush of operands or results); they resolve 2^-133, so such an operand enters rounded to the nearest
+ *     multiple of 2^-133: absolute error at most 2^-134 (relative 2^-24 at 2^-110, 2^-8 at 2^-126), zero below 2^-134.
+ *   Winograd kernels (fp32 pipe in either mode): all of fp32; a value below 2^-124 is divided by up to 4 in the transform
+ *     domain and rounds to the fp32 subnormal grid there (absolute error at most 9 x 2^-150 per output); around a non-finite
+ *     input the whole 2x2 tile is NaN.
+ * Replaces nothing in the reference (its
  * cudnn backend picks algorithms internally, models.lua:1-2); exposed so parity can be run in both modes.
  * PRECEDENCE: the Winograd bits of fg_set_fusion win over this switch -- the forward / data gradient of every layer that
  * FG_FUSE_WINOGRAD / _UP / _5X5 cover (3x3, folded up-convolutions, 5x5: most of the FLOPs of both workloads) runs the fp32 Winograd
@@ -638,7 +649,14 @@ int fg_linear_backward_data(fg_ctx* ctx, const float* gy, const float* w, float*
                             void* ws, size_t ws_bytes);
 int fg_linear_backward_weight(fg_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, float beta,
                               int batch, int in_f, int out_f, void* ws, size_t ws_bytes);
-/* SpatialBatchNormalization; slope != NULL fuses the following PReLU.  scratch >= fg_bn_scratch_floats(c) floats */
+/* SpatialBatchNormalization; slope != NULL fuses the following PReLU.  scratch >= fg_bn_scratch_floats(c) floats.
+ * Value domain of the batch statistics: one pass over d = x - pivot (pivot = row 0 of the channel) with sum d and sum d^2 in fp32
+ * partials of at most ceil(rows / min(ceil(rows / 64), 256)) rows each, everything behind the partials in fp64.  A constant channel
+ * has variance exactly 0 (invstd = 1 / sqrt(eps)); rows = 1 leaves the running variance's unbiased factor at 1.  A pivot k standard
+ * deviations from the mean costs (1 + k^2) 2^-24 relative in the variance per fp32 addition of a partial.  d^2 overflows fp32 for
+ * |x - pivot| above 1.8e19 (sqrt(FLT_MAX) = 1.8447e19), a partial once the root mean square of |x - pivot| over its rows passes
+ * 1.8447e19 / sqrt(rows of the partial): the statistics are then inf / NaN.  Pinned at max |x - pivot| = 7e17 (2^59.3) with 64 rows
+ * per partial (tests/test_gpu_value_domain.py). */
 long long fg_bn_scratch_floats(int c);
 int fg_batchnorm_forward(fg_ctx* ctx, const float* x, float* y, long long rows, int c, const float* gamma,
                          const float* beta, const float* slope, float* save_mean, float* save_invstd,
