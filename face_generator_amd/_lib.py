@@ -26,8 +26,17 @@ class LayerSpec(ctypes.Structure):
                 ("d", ctypes.c_int), ("p", ctypes.c_float), ("q", ctypes.c_float)]
 
 
+class AugmentSpec(ctypes.Structure):
+    """fg_augment_spec (include/facegen_hip.h fg_draw_transforms)"""
+    _fields_ = [("hflip", ctypes.c_int), ("vflip", ctypes.c_int), ("zoom_equal", ctypes.c_int), ("zoom_lo", ctypes.c_double),
+                ("zoom_hi", ctypes.c_double), ("rot_lo", ctypes.c_int), ("rot_hi", ctypes.c_int), ("shear_lo", ctypes.c_int),
+                ("shear_hi", ctypes.c_int), ("tx_lo", ctypes.c_int), ("tx_hi", ctypes.c_int), ("ty_lo", ctypes.c_int),
+                ("ty_hi", ctypes.c_int), ("gain_lo", ctypes.c_double), ("gain_hi", ctypes.c_double)]
+
+
 _CTYPES = [
     (r"^const fg_layer_spec\*$", ctypes.POINTER(LayerSpec)),
+    (r"^const fg_augment_spec\*$", ctypes.POINTER(AugmentSpec)),
     (r"^(const )?float\* const\*$", ctypes.POINTER(ctypes.c_void_p)),
     (r"^(fg_ctx|fg_net|fg_comm|fg_gan|fg_sampler|void|float)\*\*$", ctypes.POINTER(ctypes.c_void_p)),
     (r"^const char\*$", ctypes.c_char_p),

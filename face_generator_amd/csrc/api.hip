@@ -3,6 +3,7 @@
 #include "fg_internal.h"
 #include "conv_ops.h"
 #include "../../include/facegen_hip.h"
+#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -305,6 +306,28 @@ int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, i
                           (double)c * s * s, FG_WARP_MAX_FLOATS);
     if (n == 0) return FG_OK;
     return fg_launch_warp_c2f(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, s, cs, fine, coarse, diff, out_layout, fill);
+}
+// what is wrong with a spec, or NULL: every range lo <= hi, the integer ones at most 2^31 values wide (the pick is a 32 x 32 bit product)
+static const char* augment_spec_fault(const fg_augment_spec& s) {
+    auto wide = [](int lo, int hi) { return (long long)hi - lo + 1 > (1LL << 31); };
+    if ((s.hflip != 0 && s.hflip != 1) || (s.vflip != 0 && s.vflip != 1) || (s.zoom_equal != 0 && s.zoom_equal != 1))
+        return "hflip, vflip and zoom_equal are 0 or 1";
+    if (!std::isfinite(s.zoom_lo) || !std::isfinite(s.zoom_hi) || !(s.zoom_lo > 0.0) || s.zoom_lo > s.zoom_hi) return "the zoom range is finite, 0 < lo <= hi";
+    if (!std::isfinite(s.gain_lo) || !std::isfinite(s.gain_hi) || !(s.gain_lo >= 0.0) || s.gain_lo > s.gain_hi) return "the gain range is finite, 0 <= lo <= hi";
+    if (s.rot_lo > s.rot_hi || wide(s.rot_lo, s.rot_hi)) return "the rotation range is lo <= hi, at most 2^31 values";
+    if (s.shear_lo > s.shear_hi || s.shear_lo < -89 || s.shear_hi > 89) return "the shear range is -89 <= lo <= hi <= 89";
+    if (s.tx_lo > s.tx_hi || wide(s.tx_lo, s.tx_hi) || s.ty_lo > s.ty_hi || wide(s.ty_lo, s.ty_hi)) return "a translation range is lo <= hi, at most 2^31 values";
+    return nullptr;
+}
+int fg_draw_transforms(fg_ctx* ctx, const fg_augment_spec* spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo,
+                       float* mats, float* gains) {
+    NEED(ctx, ctx, "null ctx");
+    if (!spec || !mats || n < 0 || hs < 1 || ws < 1 || ho < 1 || wo < 1)
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_draw_transforms: bad argument (spec %s, mats %s, n=%d, %dx%d -> %dx%d)", spec ? "given" : "NULL",
+                          mats ? "given" : "NULL", n, hs, ws, ho, wo);
+    if (const char* fault = augment_spec_fault(*spec)) return fg_set_err(ctx, FG_ERR_INVALID, "fg_draw_transforms: %s", fault);
+    if (n == 0) return FG_OK;
+    return fg_launch_draw_transforms(ctx, *spec, seed, offset, n, hs, ws, ho, wo, mats, gains);
 }
 int fg_rng_uniform(fg_ctx* ctx, uint64_t seed, uint64_t off, float* o, long long n, float lo, float hi) {
     NEED(ctx, ctx && o && n >= 0, "bad argument");

@@ -579,5 +579,8 @@ struct RngSeg { float* out; long long n; uint64_t seed, offset; float lo, hi; in
 struct RngMulti { RngSeg seg[FG_RNG_MAX_SEGS]; int n; long long total_quads; };
 int fg_launch_rng_multi(fg_ctx*, RngMulti& m);   // fills q0 / total_quads; segment i == fg_launch_rng_*(seed_i, offset_i, ...)
 int fg_launch_rng_uniform(fg_ctx*, uint64_t seed, uint64_t offset, float* out, long long n, float lo, float hi);
+// fg_draw_transforms: image j takes the quads offset + 3j .. offset + 3j + 2 of the stream above; the spec is checked by the entry
+int fg_launch_draw_transforms(fg_ctx*, const fg_augment_spec& spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo,
+                              float* mats, float* gains);
 int fg_launch_rng_bernoulli(fg_ctx*, uint64_t seed, uint64_t offset, float* out, long long n, float keep_prob);
 int fg_launch_rng_normal(fg_ctx*, uint64_t seed, uint64_t offset, float* out, long long n, float mean, float std);

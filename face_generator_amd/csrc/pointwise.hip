@@ -2479,3 +2479,97 @@ int fg_launch_rng_bernoulli(fg_ctx* ctx, uint64_t seed, uint64_t offset, float* 
 int fg_launch_rng_normal(fg_ctx* ctx, uint64_t seed, uint64_t offset, float* out, long long n, float mean, float std) {
     return launch_rng(ctx, seed, offset, out, n, mean, std, 2);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// fg_draw_transforms (include/facegen_hip.h): the random transforms of n images, drawn from the Philox stream and assembled into the
+// mats / gains of fg_warp_images on the device.  One thread per image: three quads (twelve words, a fixed word per pick), the picks,
+// sin / cos of whole degrees by the header's polynomial, the closed-form inverse of runtime.Augmenter.matrix, six + one 4-byte stores.
+// All arithmetic is fp64 with every operation rounded on its own, in the header's order (no FMA contraction): a numpy float64
+// restatement matches bit for bit.  No LDS, no scratch; nothing on the device is read.
+// No new kernel name: the draw is a fourth mode of the Philox kernel, rng_kernel<FG_RNG_TRANSFORMS> -- a template beside rng_kernel
+// (whose code and launch are what they were), told apart by its first parameter; its launch line reads (rng_kernel<FG_RNG_TRANSFORMS>).
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int FG_RNG_TRANSFORMS = 3;        // after 0 uniform, 1 bernoulli, 2 normal
+// sin(x) = x * P(x*x), cos(x) = Q(x*x) for |x| <= pi/4: the Taylor coefficients (-1)^i / (2i+1)!, i = 8 .. 0, and (-1)^i / (2i)!,
+// i = 9 .. 0, each the double nearest to the quotient (the factorials are exact in fp64, the division is rounded once at compile time)
+__device__ __forceinline__ double fg_deg_sin_poly(double x) {
+#pragma clang fp contract(off)
+    constexpr double c[9] = {1.0, -1.0 / 6.0, 1.0 / 120.0, -1.0 / 5040.0, 1.0 / 362880.0, -1.0 / 39916800.0, 1.0 / 6227020800.0,
+                             -1.0 / 1307674368000.0, 1.0 / 355687428096000.0};
+    const double z = x * x;
+    double p = c[8];
+#pragma unroll
+    for (int i = 7; i >= 0; --i) p = p * z + c[i];
+    return x * p;
+}
+__device__ __forceinline__ double fg_deg_cos_poly(double x) {
+#pragma clang fp contract(off)
+    constexpr double c[10] = {1.0, -1.0 / 2.0, 1.0 / 24.0, -1.0 / 720.0, 1.0 / 40320.0, -1.0 / 3628800.0, 1.0 / 479001600.0,
+                              -1.0 / 87178291200.0, 1.0 / 20922789888000.0, -1.0 / 6402373705728000.0};
+    const double z = x * x;
+    double p = c[9];
+#pragma unroll
+    for (int i = 8; i >= 0; --i) p = p * z + c[i];
+    return p;
+}
+// sin and cos of k whole degrees: k to [0, 360), the quadrant q and r in [0, 90); the polynomial's argument never exceeds 45 degrees
+__device__ __forceinline__ void fg_deg_sincos(long long k, double& s, double& c) {
+#pragma clang fp contract(off)
+    int m = (int)(k % 360);
+    if (m < 0) m += 360;
+    const int q = m / 90, r = m % 90;
+    const double D = 0x1.1df46a2529d39p-6;
+    double s0, c0;
+    if (r <= 45) { const double x = (double)r * D; s0 = fg_deg_sin_poly(x); c0 = fg_deg_cos_poly(x); }
+    else { const double x = (double)(90 - r) * D; s0 = fg_deg_cos_poly(x); c0 = fg_deg_sin_poly(x); }
+    if (q == 0) { s = s0; c = c0; }
+    else if (q == 1) { s = c0; c = 0.0 - s0; }
+    else if (q == 2) { s = 0.0 - s0; c = 0.0 - c0; }
+    else { s = 0.0 - c0; c = s0; }
+}
+__device__ __forceinline__ long long fg_draw_int(uint32_t w, int lo, int hi) {
+    return (long long)lo + (long long)(((uint64_t)w * (uint64_t)((long long)hi - lo + 1)) >> 32);
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void rng_kernel(const fg_augment_spec sp, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo,
+                                                  float* __restrict__ mats, float* __restrict__ gains) {
+#pragma clang fp contract(off)
+    static_assert(MODE == FG_RNG_TRANSFORMS, "the modes 0 .. 2 are the arguments of the plain rng_kernel");
+    for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (long long)gridDim.x * blockDim.x) {
+        uint32_t w[12];
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const uint64_t ctr = offset + 3ull * (uint64_t)j + (uint64_t)t;
+            philox4x32((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w + 4 * t);
+        }
+        const bool hf = sp.hflip && (w[0] >> 31), vf = sp.vflip && (w[1] >> 31);
+        const double U = 1.0 / 16777216.0;
+        const double zx = sp.zoom_lo + ((double)(w[2] >> 8) * U) * (sp.zoom_hi - sp.zoom_lo);
+        const double zy = sp.zoom_equal ? zx : sp.zoom_lo + ((double)(w[3] >> 8) * U) * (sp.zoom_hi - sp.zoom_lo);
+        const long long rot = fg_draw_int(w[4], sp.rot_lo, sp.rot_hi), sh = fg_draw_int(w[5], sp.shear_lo, sp.shear_hi);
+        const long long tx = fg_draw_int(w[6], sp.tx_lo, sp.tx_hi), ty = fg_draw_int(w[7], sp.ty_lo, sp.ty_hi);
+        const double gain = sp.gain_lo + ((double)(w[8] >> 8) * U) * (sp.gain_hi - sp.gain_lo);
+        double sr, cr, srs, crs;
+        fg_deg_sincos(rot, sr, cr);
+        fg_deg_sincos(rot + sh, srs, crs);
+        const double a = zx * cr, b = 0.0 - zy * srs, c = zx * sr, d = zy * crs;
+        const double det = a * d - b * c;
+        const double ia = d / det, ib = (0.0 - b) / det, ic = (0.0 - c) / det, id = a / det;
+        const int cx = wo / 2, cy = ho / 2;
+        const double qx = (double)((long long)cx + tx), qy = (double)((long long)cy + ty);
+        double m0 = ia + 0.0, m1 = ib + 0.0, m2 = ((double)cx - (ia * qx + ib * qy)) + (double)(ws - wo) / 2.0;
+        double m3 = ic + 0.0, m4 = id + 0.0, m5 = ((double)cy - (ic * qx + id * qy)) + (double)(hs - ho) / 2.0;
+        if (hf) { m0 = 0.0 - m0; m1 = 0.0 - m1; m2 = (double)(ws - 1) - m2; }
+        if (vf) { m3 = 0.0 - m3; m4 = 0.0 - m4; m5 = (double)(hs - 1) - m5; }
+        float* o = mats + 6 * j;
+        o[0] = (float)m0; o[1] = (float)m1; o[2] = (float)m2; o[3] = (float)m3; o[4] = (float)m4; o[5] = (float)m5;
+        if (gains) gains[j] = (float)gain;
+    }
+}
+int fg_launch_draw_transforms(fg_ctx* ctx, const fg_augment_spec& spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo,
+                              float* mats, float* gains) {
+    if (n == 0) return FG_OK;
+    hipLaunchKernelGGL((rng_kernel<FG_RNG_TRANSFORMS>), FG_GRID((long long)n, 256), dim3(256), 0, ctx->stream, spec, seed, offset, n, hs, ws, ho, wo, mats, gains);
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}

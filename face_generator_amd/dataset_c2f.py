@@ -131,9 +131,10 @@ class AugmentedResult:
     def gather_fields(self, indices, fields, layout="nhwc"):
         """-> a tuple of device tensors [n][S][S][C] ("nhwc") or [n][C][S][S] ("nchw") in the order of `fields`, a subset of
         ("fine", "coarse", "diff"): field f of dataset[indices[j]] under transform j.  One Augmenter.draw of n transforms shared
-        by all fields, one upload, one launch."""
+        by all fields, one upload, one launch; a runtime.DeviceAugmenter draws on the device instead (fg_draw_transforms: no
+        host draw, no upload)."""
         from . import ops
-        from .runtime import FgError
+        from .runtime import DeviceAugmenter, FgError
         if layout not in ("nhwc", "nchw"):
             raise FgError("AugmentedResult.gather_fields: layout must be 'nhwc' or 'nchw'")
         fields = tuple(fields)
@@ -144,8 +145,11 @@ class AugmentedResult:
         if not n:
             shape = (0, s, s, ds.c) if layout == "nhwc" else (0, ds.c, s, s)
             return tuple(self.ctx.empty(*shape) for _ in fields)
-        mats, gains = self.augment.draw(n, (ds.h, ds.w))
-        both = torch.cat([torch.from_numpy(mats).reshape(-1), torch.from_numpy(gains)]).to(self.ctx.device)         # one transfer
+        if isinstance(self.augment, DeviceAugmenter):
+            both = self.augment.draw_device(self.ctx, n, (ds.h, ds.w))          # drawn where they are used: no host draw, no upload
+        else:
+            mats, gains = self.augment.draw(n, (ds.h, ds.w))
+            both = torch.cat([torch.from_numpy(mats).reshape(-1), torch.from_numpy(gains)]).to(self.ctx.device)     # one transfer
         return ops.warp_c2f(ds.images, idx, s, self.coarseScale, mats=both[:6 * n], gains=both[6 * n:], fields=fields, set_layout="nchw",
                             out_layout=layout, fill=self.augment.fill, ctx=self.ctx)
 

@@ -1,8 +1,11 @@
 """Module-level operator wrappers (NHWC device tensors) over the C ABI -- the nn.Module-protocol entries
 (updateOutput / updateGradInput / accGradParameters) of include/facegen_hip.h.  Weights are passed in REFERENCE
 layout ([O][I][kH][kW] / [out][in]); packing happens inside the library."""
+import ctypes
+
 import torch
 
+from ._lib import AugmentSpec
 from .runtime import get_context
 
 
@@ -257,6 +260,27 @@ def warp_c2f(images, indices, fine_scale, coarse_scale, mats=None, gains=None, f
                                       None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n, s, cs,
                                       P("fine"), P("coarse"), P("diff"), layouts[out_layout], fills[fill]))
     return tuple(out[f] for f in fields)
+
+
+def draw_transforms(spec, n, src_hw, out_hw, seed, offset, ctx=None):
+    """The transforms of n images drawn and assembled on the device: include/facegen_hip.h fg_draw_transforms.  spec: an
+    _lib.AugmentSpec or a runtime.DeviceAugmenter (its spec(); out_hw may then be None, the augmenter's; its own offset stays where
+    it is); src_hw = (hs, ws): the set's images, out_hw = (ho, wo): the batch's; image j owns the Philox quads offset + 3j ..
+    offset + 3j + 2 of the stream keyed by seed.  -> device float32 (mats [n][6], gains [n]), what warp_images / warp_c2f take."""
+    ctx = ctx or get_context()
+    if hasattr(spec, "spec"):
+        out_hw = spec.out_hw if out_hw is None else out_hw
+        spec = spec.spec()
+    if not isinstance(spec, AugmentSpec):
+        raise ValueError("draw_transforms: spec must be an _lib.AugmentSpec or a runtime.DeviceAugmenter")
+    n, seed, offset = int(n), int(seed), int(offset)
+    if n < 0 or not 0 <= seed < 2 ** 64 or not 0 <= offset < 2 ** 64:
+        raise ValueError("draw_transforms: n >= 0, seed and offset are 64-bit unsigned numbers")
+    both = ctx.empty(7 * n)
+    if n:                                   # (an empty tensor has no address to hand over)
+        ctx.check(ctx.lib.fg_draw_transforms(ctx.h, ctypes.byref(spec), seed, offset, n, int(src_hw[0]), int(src_hw[1]), int(out_hw[0]),
+                                             int(out_hw[1]), both.data_ptr(), both.data_ptr() + 24 * n))
+    return both[:6 * n].view(n, 6), both[6 * n:]
 
 
 def c2f_coarse_diff(fine, coarse_scale, layout="nhwc", ctx=None):

@@ -789,7 +789,8 @@ class DeviceDataset:
     def gather(self, indices, layout="nhwc", out=None, augment=True):
         """-> device [n][H][W][C] ("nhwc", what step_D / step_G and the nets take) or [n][C][H][W] ("nchw") with out[j] =
         dataset[indices[j]]; repeated indices are legal.  With an Augmenter set (and augment=True) every image comes back under a
-        fresh random transform, at the augmenter's out_hw: one draw, one upload, one launch of fg_warp_images."""
+        fresh random transform, at the augmenter's out_hw: one draw, one upload, one launch of fg_warp_images -- with a
+        DeviceAugmenter one launch of fg_draw_transforms in place of the host's draw and the upload."""
         if layout not in ("nhwc", "nchw"):
             raise FgError("DeviceDataset.gather: layout must be 'nhwc' or 'nchw'")
         if augment and self.augment is not None:
@@ -817,8 +818,11 @@ class DeviceDataset:
         elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * self.c * ho * wo:
             raise FgError("DeviceDataset.gather: out must be a contiguous float32 tensor of %d elements" % (n * self.c * ho * wo))
         if n:
-            mats, gains = aug.draw(n, (self.h, self.w))
-            both = torch.cat([torch.from_numpy(mats).reshape(-1), torch.from_numpy(gains)]).to(self.ctx.device)     # one transfer
+            if isinstance(aug, DeviceAugmenter):
+                both = aug.draw_device(self.ctx, n, (self.h, self.w))           # drawn where they are used: no host draw, no upload
+            else:
+                mats, gains = aug.draw(n, (self.h, self.w))
+                both = torch.cat([torch.from_numpy(mats).reshape(-1), torch.from_numpy(gains)]).to(self.ctx.device)     # one transfer
             self.ctx.check(self.lib.fg_warp_images(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1, idx.data_ptr(),
                                                    both.data_ptr(), both.data_ptr() + 24 * n, n, out.data_ptr(), ho, wo,
                                                    0 if layout == "nhwc" else 1, aug.fill_code))
@@ -907,3 +911,67 @@ class Augmenter:
         picks = [self.draw_one() for _ in range(n)]
         mats = np.array([self.matrix(p, src_hw) for p in picks], dtype=np.float64).reshape(n, 6)
         return mats.astype(np.float32), np.array([p[8] for p in picks], dtype=np.float64).astype(np.float32)
+
+
+class DeviceAugmenter(Augmenter):
+    """An Augmenter whose transforms are drawn, assembled into matrices and left on the device by fg_draw_transforms (include/
+    facegen_hip.h): no Python per image and no upload per batch.  The constructor takes Augmenter's arguments with its defaults, and
+    `offset`; rotation, shear and translation ranges must be whole numbers (the reference draws them with randint, and the device
+    picks integers).  `seed` keys the library's Philox4x32-10 stream -- the conventions of fg_rng_uniform -- and image j of a draw
+    owns the quads offset + 3j .. offset + 3j + 2, so the stream is (seed, offset): state() / set_state() save and restore it, and
+    every rank of a data-parallel run passes its own seed (seed=43 + rank), as it does for the host augmenter.  The numbers differ
+    from Augmenter's, which keeps its random.Random stream; S.rng is touched by neither.
+
+    DeviceDataset(.., augment=DeviceAugmenter(..)) and dataset_c2f.toResultAugmented take it wherever they take an Augmenter and
+    then call draw_device(); draw() returns the same numbers read back, for code that feeds the warp from the host."""
+
+    def __init__(self, out_hw, hflip=True, vflip=False, scale_to_percent=(0.82, 1.10), scale_axis_equally=True, rotation_deg=8,
+                 shear_deg=0, translation_x_px=None, translation_y_px=None, brightness_change=0.1, fill="constant", seed=43, offset=0):
+        Augmenter.__init__(self, out_hw, hflip=hflip, vflip=vflip, scale_to_percent=scale_to_percent, scale_axis_equally=scale_axis_equally,
+                           rotation_deg=rotation_deg, shear_deg=shear_deg, translation_x_px=translation_x_px,
+                           translation_y_px=translation_y_px, brightness_change=brightness_change, fill=fill, seed=seed)
+        for name, r in (("rotation_deg", self.rotation), ("shear_deg", self.shear), ("translation_x_px", self.tx), ("translation_y_px", self.ty)):
+            if any(float(v) != int(v) for v in r):
+                raise FgError("DeviceAugmenter: %s must be whole numbers, got %s (the picks are integers)" % (name, str(tuple(r))))
+        self.rotation, self.shear = tuple(int(v) for v in self.rotation), tuple(int(v) for v in self.shear)
+        self.tx, self.ty = tuple(int(v) for v in self.tx), tuple(int(v) for v in self.ty)
+        self.set_state(seed, offset)
+
+    def state(self):
+        """-> (seed, offset): all there is to save of the stream"""
+        return self.seed, self.offset
+
+    def set_state(self, seed, offset=0):
+        seed, offset = int(seed), int(offset)
+        if not 0 <= seed < 2 ** 64 or not 0 <= offset < 2 ** 64:
+            raise FgError("DeviceAugmenter: seed and offset are 64-bit unsigned numbers, got %d, %d" % (seed, offset))
+        self.seed, self.offset = seed, offset
+
+    def spec(self):
+        """-> the fg_augment_spec of this augmenter (a ctypes structure, _lib.AugmentSpec); the entry checks its ranges"""
+        s = _lib.AugmentSpec()
+        s.hflip, s.vflip, s.zoom_equal = int(self.hflip), int(self.vflip), int(self.scale_axis_equally)
+        s.zoom_lo, s.zoom_hi = float(self.scale[0]), float(self.scale[1])
+        (s.rot_lo, s.rot_hi), (s.shear_lo, s.shear_hi) = self.rotation, self.shear
+        (s.tx_lo, s.tx_hi), (s.ty_lo, s.ty_hi) = self.tx, self.ty
+        s.gain_lo, s.gain_hi = 1.0 - self.brightness, 1.0 + self.brightness
+        return s
+
+    def draw_one(self):
+        raise FgError("DeviceAugmenter: the picks are drawn on the device -- draw_device() or draw()")
+
+    def draw_device(self, ctx, n, src_hw):
+        """-> one device float32 tensor of 7n floats, the n matrices and then the n gains, for n images of a set whose images are
+        src_hw = (hs, ws); one launch, and the offset moves on by 3n"""
+        n, (hs, ws), (ho, wo) = int(n), (int(src_hw[0]), int(src_hw[1])), self.out_hw
+        both = ctx.empty(7 * n)
+        if n:                               # (an empty tensor has no address to hand over)
+            ctx.check(ctx.lib.fg_draw_transforms(ctx.h, ctypes.byref(self.spec()), self.seed, self.offset, n, hs, ws, ho, wo,
+                                                 both.data_ptr(), both.data_ptr() + 24 * n))
+        self.offset = (self.offset + 3 * n) % 2 ** 64
+        return both
+
+    def draw(self, n, src_hw, ctx=None):
+        """-> host float32 (mats [n][6], gains [n]): draw_device() read back (synchronises)"""
+        both = self.draw_device(ctx or get_context(), n, src_hw).cpu().numpy()
+        return both[:6 * n].reshape(n, 6).copy(), both[6 * n:].copy()

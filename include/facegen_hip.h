@@ -603,6 +603,54 @@ int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, i
                 const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout,
                 int fill);
 
+/* ---- the random transforms of dataset/generate_dataset.py (:43-48 and its create_aug_matrices: flip, zoom, rotation, shear,
+ *      translation, brightness) drawn, assembled into matrices and left on the device: the mats / gains of fg_warp_images and
+ *      fg_warp_c2f for n images in one launch, no host arithmetic and no upload per batch. ----
+ * spec: the ranges (host memory, read during the call only; it travels to the kernel by value).
+ * mats: device float [n][6], output pixel -> source pixel, exactly the meaning fg_warp_images gives it.  gains: device float [n],
+ *   or NULL: not wanted.  hs x ws: the images of the set; ho x wo: the images of the batch.
+ * Stream: image j owns the quads offset + 3j, offset + 3j + 1 and offset + 3j + 2 of the Philox4x32-10 stream of fg_rng_uniform
+ *   (counter = the quad's 64-bit number, modulo 2^64, in words 0 and 1, words 2 and 3 zero; key = seed lo / hi), twelve 32-bit
+ *   words w0 .. w11 in the order the three quads give them.  The assignment is fixed whatever the spec enables: w0 horizontal
+ *   flip, w1 vertical flip, w2 zoom x, w3 zoom y, w4 rotation, w5 shear, w6 tx, w7 ty, w8 gain, w9 .. w11 reserved.  The entry is
+ *   stateless: n images at offset followed by m images at offset + 3n are the n + m images of one call at offset.
+ * Picks: a flip iff its axis is enabled and w >> 31 == 1.  u(w) = (double)(w >> 8) * 2^-24.  zx = zoom_lo + u(w2) * (zoom_hi -
+ *   zoom_lo); zy = zx if zoom_equal, else the same with w3; gain = (float)(gain_lo + u(w8) * (gain_hi - gain_lo)).  An integer
+ *   pick (rotation and shear in whole degrees, tx and ty in whole output pixels) is
+ *     lo + (int)(((uint64_t)w * (uint64_t)(hi - lo + 1)) >> 32):  no floating point is involved.
+ * Angles: sin and cos of a whole number of degrees k are DEFINED here, not taken from a math library.  k is reduced to [0, 360);
+ *   q = k / 90, r = k % 90.  For r <= 45: x = r * D, s0 = S(x), c0 = C(x); otherwise x = (90 - r) * D, s0 = C(x), c0 = S(x);
+ *   D = 0x1.1df46a2529d39p-6 (pi / 180).  (sin, cos) = (s0, c0) for q = 0, (c0, 0.0 - s0) for 1, (0.0 - s0, 0.0 - c0) for 2,
+ *   (0.0 - c0, s0) for 3.  S(x) = x * P, P the Horner evaluation in z = x*x of the coefficients (-1)^i / (2i+1)! for i = 8 .. 0,
+ *   starting from the i = 8 term (P = c8; P = P*z + c7; ..); C(x) the Horner evaluation of (-1)^i / (2i)! for i = 9 .. 0.  Each
+ *   coefficient is the double nearest to that quotient.
+ * Matrix, runtime.Augmenter.matrix in fp64 with r the rotation and s the shear:
+ *     a = zx*cos r,  b = 0.0 - zy*sin(r+s),  c = zx*sin r,  d = zy*cos(r+s),  det = a*d - b*c,
+ *     ia = d/det,  ib = (0.0-b)/det,  ic = (0.0-c)/det,  id = a/det,
+ *     cx = wo/2,  cy = ho/2 (integer division),  qx = cx+tx,  qy = cy+ty,
+ *     m = [ia+0.0, ib+0.0, (cx-(ia*qx+ib*qy))+(ws-wo)/2.0, ic+0.0, id+0.0, (cy-(ic*qx+id*qy))+(hs-ho)/2.0];
+ *   a horizontal flip then gives m[0:3] = [0.0-m0, 0.0-m1, (ws-1)-m2], a vertical one the same for m[3:6] with hs.  Each entry is
+ *   rounded once to fp32.
+ *   All of it is fp64 and every operation is rounded on its own, in the order written (no fused multiply-add: the kernel is
+ *   compiled under `fp contract(off)`): a numpy float64 restatement equals the device bit for bit.  A neutral spec gives exactly
+ *   [1, 0, (ws-wo)/2, 0, 1, (hs-ho)/2] and gain exactly 1.
+ * Exactly mats[0 .. 6n) and gains[0 .. n) are written; nothing on the device is read.  4-byte alignment is enough.  One launch of
+ *   one kernel on the context's stream, one thread per image; no LDS, no scratch, no atomics, no synchronisation.
+ * n == 0: FG_OK, nothing is launched.  NULL ctx / spec / mats, n < 0, a size < 1, a flag other than 0 / 1, lo > hi anywhere, a
+ *   non-finite or non-positive zoom, a negative or non-finite gain, a shear outside -89 .. 89, an integer range wider than 2^31
+ *   values: FG_ERR_INVALID, the message names the entry, nothing is launched. */
+typedef struct fg_augment_spec {
+    int hflip, vflip;                   /* 0 / 1: that axis is mirrored with probability 1/2 */
+    int zoom_equal;                     /* 1: zy = zx */
+    double zoom_lo, zoom_hi;            /* finite, 0 < lo <= hi */
+    int rot_lo, rot_hi;                 /* whole degrees, lo <= hi (the reference draws randint) */
+    int shear_lo, shear_hi;             /* whole degrees, -89 <= lo <= hi <= 89 */
+    int tx_lo, tx_hi, ty_lo, ty_hi;     /* whole output pixels, lo <= hi */
+    double gain_lo, gain_hi;            /* finite, 0 <= lo <= hi */
+} fg_augment_spec;
+int fg_draw_transforms(fg_ctx* ctx, const fg_augment_spec* spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho,
+                       int wo, float* mats, float* gains);
+
 /* ---- the c2f data step in front of the train closure (dataset_c2f.lua:49-61, `dataset._toResult`) ----
  * fg_scale_bilinear = image.scale(src, width, height) of the Torch7 `image` package (default mode 'bilinear'; un-vendored luarocks
  * dependency, restated in oracle/image_scale.py): width pass then height pass; per axis up-scaling interpolates with

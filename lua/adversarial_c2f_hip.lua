@@ -45,6 +45,8 @@ local function pick(data, n, field, c, h, w)
     return out
 end
 
+-- (A set under fresh transforms per pull, FG.augmentedResult(fineImages, coarseScale, fineScale, draw), takes the reference's
+-- augmentation as `local draw = FG.augmenter(fineScale, fineScale, {seed = 43 + rank})`: drawn on the device, no host arithmetic.)
 -- the same `n` math.random draws as 1-based indices, for a set that is gathered on the device (FG.Dataset:gather)
 local function picks(data, n)
     local out = {}

@@ -150,6 +150,8 @@ int fg_nearest_update(fg_ctx* ctx, const float* queries, int q, const float* row
 int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int h, int w, int set_layout, const int* idx, int n, float* out, int out_layout);
 int fg_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill);
 int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill);
+typedef struct fg_augment_spec { int hflip, vflip; int zoom_equal; double zoom_lo, zoom_hi; int rot_lo, rot_hi; int shear_lo, shear_hi; int tx_lo, tx_hi, ty_lo, ty_hi; double gain_lo, gain_hi; } fg_augment_spec;
+int fg_draw_transforms(fg_ctx* ctx, const fg_augment_spec* spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo, float* mats, float* gains);
 int fg_scale_bilinear(fg_ctx* ctx, const float* src, float* dst, int n, int c, int hs, int ws, int hd, int wd, int layout);
 int fg_c2f_coarse_diff(fg_ctx* ctx, const float* fine, float* coarse, float* diff, float* tmp, int n, int c, int s, int cs, int layout);
 size_t fg_conv2d_workspace_bytes(int batch, int h, int w, int cin, int cout, int k, int upsample2x);
@@ -913,6 +915,65 @@ function M.augmentedResult(fineImages, coarseScale, fineScale, draw, fill)
     assert(coarseScale >= 1 and coarseScale <= fineScale, 'FG.augmentedResult: 1 <= coarseScale <= fineScale')
     local set = M.isDataset(fineImages) and fineImages or M.Dataset(fineImages)
     return setmetatable({set = set, coarseScale = coarseScale, fineScale = fineScale, draw = draw, fill = fill or 0}, Augmented)
+end
+-- fg_draw_transforms: the transforms of n images drawn and assembled on the device -> mats (n * 6 floats, output pixel -> source pixel),
+-- gains (n floats) as DeviceTensors, what M.warpImages / ds:gatherWarped / ds:gatherWarpedC2F take.  spec: an fg_augment_spec cdata or a
+-- table of its fields (include/facegen_hip.h); image j owns the Philox quads offset + 3j .. offset + 3j + 2 of the stream keyed by seed,
+-- so n images at offset and then m at offset + 3n are the n + m of one call.  hs x ws: the set's images, ho x wo: the batch's
+function M.drawTransforms(spec, seed, offset, n, hs, ws, ho, wo)
+    assert(n >= 1, 'FG.drawTransforms: n >= 1')
+    local cspec = ffi.istype('fg_augment_spec', spec) and spec or ffi.new('fg_augment_spec', spec)
+    local mats, gains = M.DeviceTensor(6 * n), M.DeviceTensor(n)
+    check(C.fg_draw_transforms(ctx, cspec, seed, offset, n, hs, ws, ho, wo, mats.ptr, gains.ptr))
+    return mats, gains
+end
+-- FG.augmenter(outH, outW, opts) -> draw, state: the augmentation of dataset/generate_dataset.py (:43-48) per batch.  opts carries the
+-- reference's names with the values of its call as defaults: hflip = true, vflip = false, scale_to_percent = {0.82, 1.10},
+-- scale_axis_equally = true, rotation_deg = 8, shear_deg = 0, translation_x_px / translation_y_px = round(5 * side / 84),
+-- brightness_change = 0.1; a range is {min, max} or one number v for -v .. v (zoom: v .. 2 - v); angles and translations are whole
+-- numbers.  Beside them seed = 43 (every rank of a data-parallel run passes 43 + its rank) and offset = 0.
+-- draw(n, hs, ws) -> mats, gains is what FG.augmentedResult takes as it is, and what ds:gatherWarped takes for its mats / gains; each
+-- call advances the offset by 3n.  state() -> seed, offset; state(seed, offset) sets them (a checkpoint saves two numbers)
+function M.augmenter(outH, outW, opts)
+    opts = opts or {}
+    local function range(v, default, negate)
+        if v == nil then v = default end
+        if type(v) == 'table' then
+            assert(#v == 2, 'FG.augmenter: a range is {min, max}')
+            return v[1], v[2]
+        end
+        if negate then return -v, v end
+        return v, 1.0 - (v - 1.0)
+    end
+    local function whole(name, lo, hi)
+        assert(lo == math.floor(lo) and hi == math.floor(hi), 'FG.augmenter: ' .. name .. ' takes whole numbers (the picks are integers)')
+        return lo, hi
+    end
+    local function flag(v, default)
+        if v == nil then v = default end
+        return v and 1 or 0
+    end
+    local spec = ffi.new('fg_augment_spec')
+    spec.hflip, spec.vflip = flag(opts.hflip, true), flag(opts.vflip, false)
+    spec.zoom_equal = flag(opts.scale_axis_equally, true)
+    spec.zoom_lo, spec.zoom_hi = range(opts.scale_to_percent, {0.82, 1.10}, false)
+    spec.rot_lo, spec.rot_hi = whole('rotation_deg', range(opts.rotation_deg, 8, true))
+    spec.shear_lo, spec.shear_hi = whole('shear_deg', range(opts.shear_deg, 0, true))
+    spec.tx_lo, spec.tx_hi = whole('translation_x_px', range(opts.translation_x_px, math.floor(5.0 * outW / 84.0 + 0.5), true))
+    spec.ty_lo, spec.ty_hi = whole('translation_y_px', range(opts.translation_y_px, math.floor(5.0 * outH / 84.0 + 0.5), true))
+    local b = opts.brightness_change or 0.1
+    spec.gain_lo, spec.gain_hi = 1.0 - b, 1.0 + b
+    local seed, offset = opts.seed or 43, opts.offset or 0
+    local function draw(n, hs, ws)
+        local mats, gains = M.drawTransforms(spec, seed, offset, n, hs, ws, outH, outW)
+        offset = offset + 3 * n
+        return mats, gains
+    end
+    local function state(newSeed, newOffset)
+        if newSeed ~= nil then seed, offset = newSeed, newOffset or 0 end
+        return seed, offset
+    end
+    return draw, state
 end
 
 return M
