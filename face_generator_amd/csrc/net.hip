@@ -921,6 +921,8 @@ static int backward_run(fg_net* n) {
     const int rc = backward_run_stages(n);
     const int rf = fg_defer_flush(ctx);
     ctx->defer = nullptr;
+    // a flush that fails at a sync-BN pause ends the pass: the caller must not reduce and resume over finals that were never written
+    if (rc == FG_PAUSED_SYNC && rf) { n->run_phase = 0; n->bwd_next = -1; return rf; }
     return rc ? rc : rf;
 }
 

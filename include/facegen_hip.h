@@ -347,7 +347,9 @@ int fg_broadcast(fg_comm* comm, float* buf, size_t n, int root);  /* identical i
  * must produce the same text: a mismatch is a hang on real hardware.
  * fg_comm_create_dry builds a communicator of `world` ranks with NO transport underneath: its collectives are recorded (tracing is
  * on from the start) and otherwise skipped, so one process -- with a planning-only context not even a GPU -- can walk the exact
- * exchange path rank `rank` of an N-GPU job takes inside fg_step_D / fg_step_G (bench.py --dry-collective). */
+ * exchange path rank `rank` of an N-GPU job takes inside fg_step_D / fg_step_G (bench.py --dry-collective).  It is valid on a
+ * device context too: a step then runs every kernel of that path and computes BatchNorm from the LOCAL batch statistics (the
+ * skipped f64 sum leaves the rank's own sums and row count), the LOCAL gradient, and the update from that gradient x 1 / world. */
 int fg_comm_create_dry(fg_ctx* ctx, int rank, int world, fg_comm** out);
 int fg_comm_set_trace(fg_comm* comm, int on);
 int fg_comm_schedule(fg_comm* comm, char* buf, size_t len, int reset);

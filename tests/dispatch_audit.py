@@ -375,6 +375,88 @@ def replay_all():
 guarded(replay_all)
 """
 
+# SYNC_CASES of tests/sync_cases.py with sync-BN on: one net per shard, each driven through its own pauses (no reduce: nothing reads
+# the buffer in a planning-only context).  Per pass the fg_net_sync_count of every pause, per shard; then the capacity refusal:
+# a buffer of 2 C doubles for the widest BatchNorm in the forward pass and, behind a forward that ran, in the backward pass.
+# Kept out of net_replay: the ledger holds the four sync kernels as `other-entry`, launched by no replay of the coverage audit.
+SYNC_PASSES = ("fwd", "eval", "fwd2", "bwd3", "bwd1", "bwd2", "range")
+SYNC_REPLAY = NET_ENGINE + r"""
+import sync_cases as SC
+def run_sync(c):
+    job = dict(list="SYNC_CASES", kind="net", case=c.name, dims=list(c.dims), layers=[list(l) for l in c.layers], batch=c.batch,
+               shards=list(c.shards), math=c.math, fusion=c.fusion, shape=[])
+    settings(job)
+    layers, (ci, hh, w) = [NC.pad(l) for l in c.layers], c.dims
+    res = dict(job, rc={}, log={}, pauses={}, cap={})
+    launches()
+    def done(p, rc):
+        if p not in res["rc"] or not res["rc"][p][0]:
+            res["rc"][p] = [rc, lib.fg_last_error(ctx.h).decode() if rc else ""]
+        res["log"].setdefault(p, []).extend(launches())
+        return rc
+    cap = SC.capacity(c)
+    sync = torch.empty(cap, dtype=torch.float64)
+    for B in c.shards:
+        h, off = ctypes.c_void_p(), ctypes.c_longlong()
+        ctx.check(lib.fg_net_create(ctx.h, make_specs(layers), len(layers), ci, hh, w, ctypes.byref(h)))
+        n, nbuf, ns = lib.fg_net_num_params(h), lib.fg_net_num_buffers(h), lib.fg_net_num_stages(h)
+        res["stages"] = ns
+        P, G, Bf = torch.empty(max(n, 1)), torch.empty(max(n, 1)), torch.empty(max(nbuf, 1))
+        ctx.check(lib.fg_net_bind(h, P.data_ptr(), G.data_ptr(), Bf.data_ptr()))
+        nb = lib.fg_net_workspace_bytes(h, B)
+        ws, x = torch.empty((nb + 3) // 4), torch.empty(B * ci * hh * w)
+        gx = torch.empty(x.numel())
+        oc, oh, ow = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        lib.fg_net_out_dims(h, ctypes.byref(oc), ctypes.byref(oh), ctypes.byref(ow))
+        gy = torch.empty(B * oc.value * oh.value * ow.value)
+        nm = lib.fg_net_num_masks(h)
+        ms = [torch.ones(max(1, lib.fg_net_mask_elems(h, i, B))) for i in range(nm)]
+        mp = (ctypes.c_void_p * max(nm, 1))(*[m.data_ptr() for m in ms])
+        F = lambda train: lib.fg_net_forward(h, B, x.data_ptr(), ws.data_ptr(), nb, train, mp if nm else None, nm, ctypes.byref(off))
+        FR = lambda: lib.fg_net_forward_resume(h, ctypes.byref(off))
+        R = lambda fl, a, b: lib.fg_net_backward_range(h, B, x.data_ptr(), gy.data_ptr(), ws.data_ptr(), nb, fl, gx.data_ptr(), a, b)
+        BR = lambda: lib.fg_net_backward_resume(h)
+        def drive(rc, resume, counts):
+            while rc == 1:
+                counts.append(lib.fg_net_sync_count(h)); rc = resume()
+            return rc
+        def run(p, start, resume):
+            counts = []
+            rc = done(p, drive(start(), resume, counts))
+            res["pauses"].setdefault(p, []).append(counts)
+            return rc
+        done("plain", F(1))              # sync off, at the shard's batch: does the producer's epilogue carry the statistics?
+        ctx.check(lib.fg_net_set_sync_bn(h, 1, sync.data_ptr(), cap))
+        ok = not run("fwd", lambda: F(1), FR) and not run("eval", lambda: F(0), FR) and not run("fwd2", lambda: F(1), FR)
+        if ok:
+            for fl in (3, 1, 2):
+                run("bwd%%d" %% fl, lambda: R(fl, ns - 1, 0), BR)
+            rc, per = 0, []
+            for s in range(1, ns):
+                counts = []
+                rc = rc or drive(R(3, ns - 1, s), BR, counts) or drive(R(3, s - 1, 0), BR, counts)
+                per.append(counts)
+            done("range", rc)
+            res["pauses"].setdefault("range", []).append(per)
+            # the capacity refusal, backward: the forward above ran to its end
+            ctx.check(lib.fg_net_set_sync_bn(h, 1, sync.data_ptr(), cap - 1))
+            counts = []
+            rc = drive(R(3, ns - 1, 0), BR, counts)
+            res["cap"].setdefault("bwd", []).append([rc, lib.fg_last_error(ctx.h).decode() if rc else "", counts, BR()])
+            # ... forward, then what follows it
+            counts = []
+            rc = drive(F(1), FR, counts)
+            row = [rc, lib.fg_last_error(ctx.h).decode() if rc else "", counts, FR(), R(3, ns - 1, 0)]
+            ctx.check(lib.fg_net_set_sync_bn(h, 1, sync.data_ptr(), cap))
+            row.append(drive(F(1), FR, []))
+            res["cap"].setdefault("fwd", []).append(row)
+            res["log"].setdefault("cap", []).extend(launches())
+        lib.fg_net_destroy(h)
+    os.ftruncate(LOG.fileno(), 0); RD.seek(0)
+    print(json.dumps(res), flush=True)
+guarded(lambda: [run_sync(c) for c in SC.SYNC_CASES])
+"""
+
 
 # whole G / D pairs (tests/gan_cases.py) at the step level: both nets and the step object created with workspaces of exactly
 # fg_net_workspace_bytes / fg_gan_workspace_bytes, then per batch and per way of giving noise and masks (NULL: drawn by the library;
@@ -548,6 +630,52 @@ guarded(replay_all)
 """
 
 
+# SYNC_STEP_CASES of tests/sync_cases.py: the BN-bearing GAN_CASES on a transport-less communicator, rank 0 of 2, with sync-BN on --
+# every iteration's D-step and G-step with explicit noise and masks, fg_gan_finish_pending behind each when the exchange overlaps.
+# One JSON line per (case, overlap, bucket target): the text of fg_comm_schedule over the whole run and the launch log.
+SYNC_GAN_REPLAY = GAN_ENGINE + r"""
+import sync_cases as SC
+from face_generator_amd.distributed import DryCollective
+def run_sync_pair(c, overlap, bucket):
+    settings(dict(math=0, fusion=%(default)d))
+    job = dict(list="SYNC_STEP_CASES", kind="gan", case=c.name, gdims=list(c.gdims), glayers=[list(l) for l in c.glayers], ddims=list(c.ddims),
+               dlayers=[list(l) for l in c.dlayers], table=c.table, max_batch=c.max_batch, batches=list(c.iters), shape=[], math=0, fusion=%(default)d,
+               cfg=dict(optD=list(c.optD), optG=list(c.optG), pen=c.pen, bucket=0), overlap=overlap, bucket=bucket)
+    res = dict(job, rc={}, log={})
+    launches()
+    pr = Pair(job)
+    coll = DryCollective(ctx, 0, 2)
+    ctx.check(lib.fg_gan_set_comm(pr.gan.h, coll.h, 1, overlap))
+    target = SC.bucket_target(bucket, lib.fg_net_num_params(pr.dnG.h))
+    if target:
+        ctx.check(lib.fg_test_set_gan_bucket_target(pr.gan.h, target))
+    rc = 0
+    for B in c.iters:
+        for which in "DG":
+            rc = rc or pr.call(which, B, True)
+            if overlap:
+                rc = rc or lib.fg_gan_finish_pending(pr.gan.h)
+    res["rc"]["run"] = [rc, lib.fg_last_error(ctx.h).decode() if rc else ""]
+    res["schedule"] = coll.schedule(reset=True)
+    res["log"]["run"] = launches()
+    ctx.check(lib.fg_gan_set_comm(pr.gan.h, None, 0, 1))
+    coll.close()
+    os.ftruncate(LOG.fileno(), 0); RD.seek(0)
+    print(json.dumps(res), flush=True)
+guarded(lambda: [run_sync_pair(GC.BY_NAME[n], ov, bk) for n in SC.SYNC_STEP_CASES for ov, bk in SC.step_settings(n)])
+"""
+
+
+@memo
+def sync_gan_replay():
+    """SYNC_STEP_CASES x SC.step_settings on a dry two-rank communicator with sync-BN on -> parsed jobs with `schedule` (the lines of
+    fg_comm_schedule over the whole run)"""
+    p = _run_stdout(SYNC_GAN_REPLAY)
+    out, err = p.communicate(timeout=600)
+    assert p.returncode == 0, err[-3000:]
+    return _parse_net_jobs(out.splitlines())
+
+
 @memo
 def gan_replay():
     """GAN_CASES and REFUSED_GAN_CASES of tests/gan_cases.py under each case's own optimizers and penalties -> parsed jobs (full launch
@@ -622,6 +750,16 @@ def _run_stdout(code, args=(), out=subprocess.PIPE):
 def net_replay():
     """NET_CASES and REFUSED_CASES of tests/net_cases.py under each case's own settings -> parsed jobs (full launch lines)"""
     p = _run_stdout(NET_REPLAY)
+    out, err = p.communicate(timeout=600)
+    assert p.returncode == 0, err[-3000:]
+    return _parse_net_jobs(out.splitlines())
+
+
+@memo
+def sync_replay():
+    """SYNC_CASES of tests/sync_cases.py with sync-BN on -> parsed jobs (full launch lines) with `pauses` {pass: [[sync_count per
+    pause] per shard]} and `cap` {"fwd" / "bwd": [row per shard]} (the rows: SYNC_REPLAY above)"""
+    p = _run_stdout(SYNC_REPLAY)
     out, err = p.communicate(timeout=600)
     assert p.returncode == 0, err[-3000:]
     return _parse_net_jobs(out.splitlines())

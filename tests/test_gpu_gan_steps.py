@@ -20,6 +20,7 @@ import torch
 
 import gan_cases as GC
 import net_cases as NC
+import sync_cases as SC
 from gpu_util import close, dev, assert_net_bars, BAR
 from mem_contract import Arena
 
@@ -143,8 +144,12 @@ def oracle_masks(case, dev_masks, B):
 class Run:
     """one case on the device and in the oracle, closure by closure"""
 
-    def __init__(self, ctx, case, comm=None, arena=True):
+    def __init__(self, ctx, case, comm=None, arena=True, sync_bn=0, overlap=None, gscale=1.0):
+        """sync_bn, overlap: what fg_gan_set_comm gets beside `comm` (overlap: default the case's own); gscale: the 1 / world by which
+        gan_optimize scales the gradient in front of penalty and clamp (fg_prep_grad) -- check_update applies it to the device's raw
+        gradient in the same place"""
         self.ctx, self.case = ctx, case
+        self.overlap, self.gscale = (case.overlap if overlap is None else overlap), gscale
         self.st = GC.oracle_gan(case, np.float64)
         self.real_opt = self.st.opt
         self.raw_opt = dict(self.st.opt, D_L1=0.0, D_L2=0.0, G_L1=0.0, G_L2=0.0, D_clamp=0.0, G_clamp=0.0)
@@ -155,8 +160,8 @@ class Run:
         load(self.st, self.gan)
         if arena:
             self.gan.dnG.ws.fill_(float("nan")); self.gan.dnD.ws.fill_(float("nan"))
-        if case.overlap is not None and comm is not None:
-            ctx.check(ctx.lib.fg_gan_set_comm(self.gan.h, comm, 0, case.overlap))
+        if self.overlap is not None and comm is not None:
+            ctx.check(ctx.lib.fg_gan_set_comm(self.gan.h, comm, sync_bn, self.overlap))
         self.noise_off, self.mask_off = 0, 0
         self.held = None
         self.global_conf = [0, 0, 0, 0]
@@ -190,7 +195,7 @@ class Run:
             gan.step_D(B, op.image(op.real, inp["real"]), cr, cf, nz, md, flags)
         else:
             gan.step_G(B, op.image(op.cond, inp["cond"]) if case.table else None, nz, md, flags)
-        if case.overlap:
+        if self.overlap:
             gan.finish_pending()               # D's deferred update lands here, inside the closure that formed its gradient
         self.guards(what)
         # ---- what the library drew: the documented streams, then the oracle's inputs ------------------------------------------------
@@ -288,7 +293,7 @@ class Run:
         dn = gan.dnD if which == "D" else gan.dnG
         method = (case.optD if which == "D" else case.optG)[0]
         p64 = p0.cpu().numpy().astype(np.float64)
-        gp = GC.penalised(case.pen, which, p64, g_dev.astype(np.float64))
+        gp = GC.penalised(case.pen, which, p64, g_dev.astype(np.float64) * self.gscale)     # scale, then penalty, then clamp: fg_prep_grad
         x1, s1 = GC.apply_rule(case, which, p64, gp, s0.cpu().numpy(), t0)
         assert gan.steps(w) == t0 + 1, "%s: step count %d behind an update at %d" % (what, gan.steps(w), t0)
         (pa, pr), parts = OPT_BARS[method]
@@ -582,6 +587,54 @@ def test_overlap_on_a_one_rank_communicator_gives_the_bits_of_no_communicator(ct
     ga, gb = a["gG"].cpu().numpy().astype(np.float64), b["gG"].cpu().numpy().astype(np.float64)
     for k in differ:
         assert abs(ga[k] - gb[k]) <= 1e-4 * abs(ga[k]) + 1e-7, (k, ga[k], gb[k])
+
+
+@pytest.fixture(scope="module")
+def planned_schedules():
+    """{(case, overlap, bucket): lines of fg_comm_schedule} from ONE planning-only child process (tests/dispatch_audit.py
+    sync_gan_replay): the text every rank of the job must produce"""
+    import dispatch_audit as A
+    return {(j["case"], j["overlap"], j["bucket"]): j["schedule"] for j in A.sync_gan_replay()}
+
+
+@pytest.mark.parametrize("name", SC.SYNC_STEP_CASES)
+def test_sync_bn_steps_on_a_dry_two_rank_communicator(ctx, name, planned_schedules):
+    """The step-level sync path on one GPU: a transport-less communicator (fg_comm_create_dry), rank 0 of 2, on the device context makes
+    fg_gan_set_comm(..., sync_bn = 1, ...) stick.  gan_drain then pauses under fg_net_forward_to (G's redirected output), under D's
+    passes and under the bucketed fg_net_backward_range of G; D's update is deferred (overlap 1); gan_optimize scales by 1 / 2.  Every
+    collective is recorded and skipped, so BatchNorm sees the local batch and the gradient stays local: the float64-oracle comparison
+    of Run.closure applies unchanged, the update from the device's gradient x 1 / 2.  Overlap 0 and 1 give the same bits; the runs
+    with G's backward cut into buckets are held to the oracle alone (a cut at a PReLU stage moves its backward out of the
+    neighbour's epilogue).  The schedule recorded on the device is the text the planning-only context gives for the same settings."""
+    from face_generator_amd.distributed import DryCollective
+    base = GC.BY_NAME[name]._replace(masks="explicit", overlap=None, bucket=0)
+    assert any(l[0] == "BATCHNORM" for l in base.glayers + base.dlayers)
+    img = int(np.prod(base.ddims))
+    nP = GC.oracle_gan(base).pG.size
+    final = {}
+    for overlap, bucket in SC.step_settings(name):
+        case = base._replace(bucket=SC.bucket_target(bucket, nP))
+        coll = DryCollective(ctx, 0, SC.STEP_WORLD)
+        run = Run(ctx, case, coll.h, sync_bn=1, overlap=overlap, gscale=1.0 / SC.STEP_WORLD)
+        try:
+            sb = run.gan.view("SYNC_BUF")
+            assert sb.numel() >= 2 * max(SC.step_f64_counts(case)), "FG_GAN_SYNC_BUF of %d floats" % sb.numel()
+            for it in range(len(case.iters)):
+                run.closure(it, "D")
+                run.closure(it, "G")
+            assert not run.gan.pending()
+            final[overlap, bucket] = snapshot(run.gan, case.iters[-1], img)
+            got = coll.schedule(reset=True)
+            want = planned_schedules[name, overlap, bucket]
+            assert got == want, "%s overlap %d bucket %s: the schedule on the device\n%s\nthe planning-only one\n%s" % (name, overlap, bucket, "\n".join(got), "\n".join(want))
+            f64 = [int(l.split()[3]) for l in got if l.split()[2] == "f64"]
+            assert f64 == SC.step_f64_counts(case) and f64, (name, f64)
+        finally:
+            ctx.check(ctx.lib.fg_gan_set_comm(run.gan.h, None, 0, 1))
+            coll.close()
+    a, b = final[0, None], final[1, None]
+    keys = ("pG", "pD", "optD", "optG", "bnG", "bnD")
+    same({k: a[k] for k in keys}, {k: b[k] for k in keys}, "%s: overlap 1 against overlap 0" % name)
 
 
 def test_nesterov_with_dampening_is_refused(ctx):
