@@ -307,6 +307,35 @@ int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, i
     if (n == 0) return FG_OK;
     return fg_launch_warp_c2f(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, s, cs, fine, coarse, diff, out_layout, fill);
 }
+int fg_warp_faces(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                  const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    const bool outputs = cs > 0 ? fine || coarse || diff : fine && !coarse && !diff;
+    if (!set || !idx || !outputs || n_set < 1 || c < 1 || hs < 1 || ws < 1 || hw < 1 || ww < 1 || s < 1 || cs < 0 || cs > s || n < 0 ||
+        (set_layout != 0 && set_layout != 1) || (out_layout != 0 && out_layout != 1) || (fill != 0 && fill != 1))
+        return fg_set_err(ctx, FG_ERR_INVALID,
+                          "fg_warp_faces: bad argument (n_set=%lld c=%d %dx%d -> window %dx%d -> %dx%d, coarse %dx%d, n=%d layouts %d -> %d fill=%d%s)",
+                          n_set, c, hs, ws, hw, ww, s, s, cs, cs, n, set_layout, out_layout, fill,
+                          outputs ? "" : cs > 0 ? ", no output" : ", cs = 0 takes fine alone");
+    if (!mats && (hw != hs || ww != ws))
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_faces: without matrices the window has the photo's size, not %dx%d -> %dx%d", hs, ws, hw, ww);
+    // (products of two ints at a time: three could pass 2^63)
+    if ((long long)c * hs >= (1LL << 31) || (long long)c * hs * ws >= (1LL << 31))
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_faces: a photo of %d x %d x %d floats is 2^31 floats or more", c, hs, ws);
+    const long long lim = FG_FACES_MAX_LDS / 4;
+    const bool small = (long long)c * hw <= lim && (long long)c * hw * ww <= lim && (long long)c * s <= lim && (long long)c * s * s <= lim;
+    if (!small)                             // (one of the images alone is above the limit; the sum below could pass 2^63)
+        return fg_set_err(ctx, FG_ERR_UNSUPPORTED,
+                          "fg_warp_faces: a window of %d x %d x %d or a face of %d x %d x %d floats alone is above the %d bytes of LDS of a "
+                          "compute unit", c, hw, ww, c, s, s, FG_FACES_MAX_LDS);
+    if (fg_warp_faces_lds_bytes(c, hw, ww, s, cs) > FG_FACES_MAX_LDS)
+        return fg_set_err(ctx, FG_ERR_UNSUPPORTED,
+                          "fg_warp_faces: a window of %d x %d x %d, a face of %d x %d x %d and a coarse image of %d x %d x %d floats with their "
+                          "%lld scale plans take %lld bytes, above the %d bytes of LDS of a compute unit",
+                          c, hw, ww, c, s, s, c, cs, cs, 3LL * s + cs, (long long)fg_warp_faces_lds_bytes(c, hw, ww, s, cs), FG_FACES_MAX_LDS);
+    if (n == 0) return FG_OK;
+    return fg_launch_warp_faces(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, hw, ww, s, cs, fine, coarse, diff, out_layout, fill);
+}
 // what is wrong with a spec, or NULL: every range lo <= hi, the integer ones at most 2^31 values wide (the pick is a 32 x 32 bit product)
 static const char* augment_spec_fault(const fg_augment_spec& s) {
     auto wide = [](int lo, int hi) { return (long long)hi - lo + 1 > (1LL << 31); };

@@ -443,6 +443,15 @@ int fg_launch_warp_images(fg_ctx*, const float* set, long long n_set, int c, int
 // diff may each be null (not written).  c * hs * ws and c * s * s <= FG_WARP_MAX_FLOATS: up to 135 KB of LDS, the limit raised per context
 int fg_launch_warp_c2f(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
                        const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw, int edge);
+// fg_warp_faces: the warp of a photo of any size (taps from global memory) into an hw x ww window in LDS, the window scaled to s x s,
+// then fg_warp_c2f's fields (cs > 0).  fg_warp_faces_lds_bytes(..) <= FG_FACES_MAX_LDS, the whole LDS of a compute unit, is the
+// entry's check and the launch's dynamic LDS; FG_SCALE_PLAN_BYTES is sizeof(ScaleTerm) (asserted beside the kernel)
+#define FG_FACES_MAX_LDS 163840
+#define FG_SCALE_PLAN_BYTES 28
+size_t fg_warp_faces_lds_bytes(int c, int hw, int ww, int s, int cs);
+int fg_launch_warp_faces(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                         const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw,
+                         int edge);
 int fg_launch_zero_insert2(fg_ctx*, const float* g, float* out, int B, int H, int W, int C);   // g [B][H][W][C] -> out [B][2H][2W][C]
 
 // thin convolutions (3 <-> wide channels), NHWC, stride 1, "same" pad, odd k <= 7

@@ -2166,9 +2166,11 @@ __device__ __forceinline__ void wi_load(const float* __restrict__ s, float* __re
         }
     }
 }
-// the warp of the LDS image `img` under mats[j] / gains[j]: store(p, ch, v) takes channel ch of output pixel p = y * wo + x.  Waits
-// for the block's copy of the image (one __syncthreads) before the first tap
-template <bool SET_NCHW, typename Store>
+// the warp of the image `img` under mats[j] / gains[j]: store(p, ch, v) takes channel ch of output pixel p = y * wo + x.  Waits
+// for the block's copy of the image (one __syncthreads) before the first tap.  LDS_IMG: `img` is the block's LDS copy, and a tap
+// outside the image reads pixel 0 and drops it; otherwise `img` is the image where it lies in the set (faces_image: a photo of any
+// size, taps straight from global memory) and such a tap addresses nothing.  The arithmetic is one
+template <bool SET_NCHW, bool LDS_IMG = true, typename Store>
 __device__ __forceinline__ void wi_warp(const float* __restrict__ img, const float* __restrict__ mats, const float* __restrict__ gains, int j,
                                         int c, int hs, int ws, int ho, int wo, int edge, int tid, Store store) {
 #pragma clang fp contract(off)
@@ -2204,11 +2206,12 @@ __device__ __forceinline__ void wi_warp(const float* __restrict__ img, const flo
             if (yb && xr) od = at + ws + 1;
         }
         const int ts = SET_NCHW ? 1 : c, cs = SET_NCHW ? Ps : 1;            // strides of a pixel and of a channel in the LDS image
-        // (a tap outside the image reads the LDS copy of pixel 0 and drops it: four reads in flight per channel, no branch)
+        // (a tap outside an LDS image reads the copy of pixel 0 and drops it: four reads in flight per channel, no branch)
         const int ia = (oa < 0 ? 0 : oa) * ts, ib = (ob < 0 ? 0 : ob) * ts, ic = (oc < 0 ? 0 : oc) * ts, id = (od < 0 ? 0 : od) * ts;
         for (int ch = 0; ch < c; ++ch) {
             const float* pl = img + ch * cs;
-            const float ra = pl[ia], rb = pl[ib], rc = pl[ic], rd = pl[id];
+            const float ra = LDS_IMG || oa >= 0 ? pl[ia] : 0.f, rb = LDS_IMG || ob >= 0 ? pl[ib] : 0.f;
+            const float rc = LDS_IMG || oc >= 0 ? pl[ic] : 0.f, rd = LDS_IMG || od >= 0 ? pl[id] : 0.f;
             const float a = oa >= 0 ? ra : 0.f, b = ob >= 0 ? rb : 0.f, cc = oc >= 0 ? rc : 0.f, d = od >= 0 ? rd : 0.f;
             const float top = a + (b - a) * fx, bot = cc + (d - cc) * fx;
             float v = top + (bot - top) * fy;
@@ -2316,12 +2319,121 @@ __device__ __forceinline__ void c2f_image(const float* __restrict__ set, float* 
         if (x >= s) { x -= s; ++y; }
     }
 }
+// fg_warp_faces (include/facegen_hip.h), the WARP = 3 instances of scale_bilinear_kernel: the reference's pipeline on a photo of any
+// size, one block per face.  The photo stays in
+// global memory: wi_warp takes the four taps of every channel of a window pixel straight from it (lanes on neighbouring window
+// pixels read neighbouring addresses of a channel-major photo; a pixel's c floats are adjacent in a pixel-major one) and stores the
+// hw x ww window into LDS, channel-major.  From there on the block is c2f_image's: LDS holds A, the window (after stage 2 the
+// cs x cs image), B, the s x s face, and T, the scale plans, taken once per block:
+//   T[0 .. s): cs -> s,  T[s .. s + cs): s -> cs,  T[s + cs .. 2s + cs): ww -> s (columns),  T[2s + cs .. 3s + cs): hw -> s (rows).
+// Stage 2 is scale_bilinear_kernel's WARP = 0 body per face element (width pass nested in height pass); with hw == ww == s the warp
+// writes the face itself.  With cs == 0 the face goes straight to `fine` and nothing follows.
+template <bool SET_NCHW, bool OUT_NCHW>
+__device__ __forceinline__ void faces_image(const float* __restrict__ set, long long n_set, int c, int hs, int ws,
+                                            const int* __restrict__ idx, const float* __restrict__ mats,
+                                            const float* __restrict__ gains, int hw, int ww, int s, int cs,
+                                            float* __restrict__ fine, float* __restrict__ coarse, float* __restrict__ diff,
+                                            int edge) {
+#pragma clang fp contract(off)
+    extern __shared__ float4 wi_lds[];
+    const int tid = (int)threadIdx.x, j = (int)blockIdx.x;
+    const int Pw = hw * ww, Po = s * s, Pc = cs * cs, Ew = c * Pw, Eo = c * Po, Ec = c * Pc;
+    float* A = reinterpret_cast<float*>(wi_lds);
+    float* B = A + (((Ew > Ec ? Ew : Ec) + 3) & ~3);
+    ScaleTerm* T = reinterpret_cast<ScaleTerm*>(B + Eo);
+    const long long base = (long long)j * Eo;
+    if (fine) fine += base;
+    if (coarse) coarse += base;
+    if (diff) diff += base;
+    const int i = idx[j];
+    if (i < 0 || (long long)i >= n_set) {                                   // outside the set: nothing is read, every requested image is NaN
+        for (int e = tid; e < Eo; e += 256) {
+            if (fine) fine[e] = gi_nan();
+            if (coarse) coarse[e] = gi_nan();
+            if (diff) diff[e] = gi_nan();
+        }
+        return;
+    }
+    const float* photo = set + (long long)i * ((long long)c * hs * ws);
+    for (int k = tid; k < 3 * s + cs; k += 256)
+        T[k] = k < s ? fg_scale_plan(cs, s, k) : k < s + cs ? fg_scale_plan(s, cs, k - s)
+             : k < 2 * s + cs ? fg_scale_plan(ww, s, k - s - cs) : fg_scale_plan(hw, s, k - 2 * s - cs);
+    // an element of the face: into B, or, without the coarse-to-fine fields, to its place in `fine`
+    auto face = [&](int p, int ch, float v) {
+        if (cs) B[ch * Po + p] = v;
+        else fine[OUT_NCHW ? ch * Po + p : p * c + ch] = v;
+    };
+    const bool copy = hw == s && ww == s;
+    if (copy) wi_warp<SET_NCHW, false>(photo, mats, gains, j, c, hs, ws, s, s, edge, tid, face);
+    else {
+        wi_warp<SET_NCHW, false>(photo, mats, gains, j, c, hs, ws, hw, ww, edge, tid, [&](int p, int ch, float v) { A[ch * Pw + p] = v; });
+        __syncthreads();                                                    // the window is complete (the plans since wi_warp's barrier)
+        int y = tid / s, x = tid - y * s;
+        const int qy = 256 / s, rx = 256 - qy * s;
+        for (int p = tid; p < Po; p += 256) {
+            const ScaleTerm th = T[s + cs + x], tv = T[2 * s + cs + y];
+            for (int ch = 0; ch < c; ++ch) {
+                const float* plane = A + ch * Pw;
+                face(p, ch, fg_scale_eval(tv, [&](int r) {
+                    const float* row = plane + r * ww;
+                    return fg_scale_eval(th, [&](int q) { return row[q]; });
+                }));
+            }
+            x += rx; y += qy;
+            if (x >= s) { x -= s; ++y; }
+        }
+    }
+    if (!cs) return;
+    __syncthreads();                                                        // B is complete, A is free
+    {
+        int y = tid / cs, x = tid - y * cs;
+        const int qy = 256 / cs, rx = 256 - qy * cs;
+        for (int p = tid; p < Pc; p += 256) {
+            const ScaleTerm th = T[s + x], tv = T[s + y];
+            for (int ch = 0; ch < c; ++ch) {
+                const float* plane = B + ch * Po;
+                A[ch * Pc + p] = fg_scale_eval(tv, [&](int r) {
+                    const float* row = plane + r * s;
+                    return fg_scale_eval(th, [&](int q) { return row[q]; });
+                });
+            }
+            x += rx; y += qy;
+            if (x >= cs) { x -= cs; ++y; }
+        }
+    }
+    __syncthreads();
+    int y = tid / s, x = tid - y * s;
+    const int qy = 256 / s, rx = 256 - qy * s;
+    for (int p = tid; p < Po; p += 256) {
+        const ScaleTerm th = T[x], tv = T[y];
+        for (int ch = 0; ch < c; ++ch) {
+            const float* plane = A + ch * Pc;
+            const float v = fg_scale_eval_up(tv, [&](int r) {
+                const float* row = plane + r * cs;
+                return fg_scale_eval_up(th, [&](int q) { return row[q]; });
+            });
+            const float f = B[ch * Po + p];
+            const int o = OUT_NCHW ? ch * Po + p : p * c + ch;
+            if (coarse) coarse[o] = v;
+            if (diff) diff[o] = f - v;
+            if (fine) fine[o] = f;
+        }
+        x += rx; y += qy;
+        if (x >= s) { x -= s; ++y; }
+    }
+}
 template <int WARP = 0, bool SET_NCHW = false, bool OUT_NCHW = false>
 __global__ __launch_bounds__(256) void scale_bilinear_kernel(const float* __restrict__ src, float* __restrict__ dst, long long total, int C, int Hs,
                                                              int Ws, int Hd, int Wd, int nchw, const float* __restrict__ sub_from,
                                                              float* __restrict__ diff, const int* __restrict__ picks, const float* __restrict__ gains,
                                                              int edge, float* __restrict__ coarse) {
-    if constexpr (WARP == 2) {
+    if constexpr (WARP == 3) {
+        // as WARP = 2, with nchw: the window as 32 unsigned bits, hw in the low 16 and ww in the high 16 (each at most
+        // FG_FACES_MAX_LDS / 4 = 40960 < 65536; ww may pass 32767, so neither the packing nor the shift is signed)
+        const unsigned win = (unsigned)nchw;
+        faces_image<SET_NCHW, OUT_NCHW>(src, total, C, Hs, Ws, picks, sub_from, gains, (int)(win & 0xffffu), (int)(win >> 16), Hd, Wd, dst, coarse,
+                                        diff, edge);
+    } else if constexpr (WARP == 2) {
         // as WARP = 1, with dst: fine, Hd: s, Wd: cs; coarse is used by these instances alone
         c2f_image<SET_NCHW, OUT_NCHW>(src, dst, coarse, diff, picks, sub_from, gains, total, C, Hs, Ws, Hd, Wd, edge, nchw);
     } else if constexpr (WARP == 1) {
@@ -2396,6 +2508,39 @@ int fg_launch_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, in
     C2F(false, true)
     C2F(false, false)
 #undef C2F
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
+// fg_warp_faces: one block per face, the exact count.  LDS: fg_warp_faces_lds_bytes (<= FG_FACES_MAX_LDS, checked by the entry); the
+// limit of each instance is raised once per context
+size_t fg_warp_faces_lds_bytes(int c, int hw, int ww, int s, int cs) {
+    const size_t Ew = (size_t)c * hw * ww, Ec = (size_t)c * cs * cs;
+    return (((((Ew > Ec ? Ew : Ec) + 3) & ~(size_t)3) + (size_t)c * s * s) * sizeof(float) + ((size_t)3 * s + cs) * sizeof(ScaleTerm) + 15) & ~(size_t)15;
+}
+int fg_launch_warp_faces(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                         const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw,
+                         int edge) {
+    static_assert(sizeof(ScaleTerm) == FG_SCALE_PLAN_BYTES, "the header of fg_warp_faces states the size of a scale plan");
+    const size_t lds = fg_warp_faces_lds_bytes(c, hw, ww, s, cs);
+    const dim3 images((unsigned)n);
+    // the window travels in the kernel's `nchw` argument: hw and ww are at most FG_FACES_MAX_LDS / 4 < 65536 (the entry's check),
+    // 16 unsigned bits each
+    const int win = (int)((unsigned)hw | ((unsigned)ww << 16));
+    if (c == 1) set_nchw = out_nchw = 1;
+#define FACES(SN, ON)                                                                                                           \
+    if ((set_nchw != 0) == SN && (out_nchw != 0) == ON) {                                                                        \
+        static char attr_key;                                                                                                    \
+        if (fg_attr_first(ctx, &attr_key))                                                                                       \
+            FG_HIP(ctx, hipFuncSetAttribute((const void*)scale_bilinear_kernel<3, SN, ON>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                            (int)FG_FACES_MAX_LDS));                                                             \
+        hipLaunchKernelGGL((scale_bilinear_kernel<3, SN, ON>), images, dim3(256), lds, ctx->stream, set, fine, n_set, c, hs, ws, s, cs, \
+                           win, mats, diff, idx, gains, edge, coarse);                                                           \
+    }
+    FACES(true, true)
+    FACES(true, false)
+    FACES(false, true)
+    FACES(false, false)
+#undef FACES
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }

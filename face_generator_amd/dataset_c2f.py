@@ -181,6 +181,72 @@ def toResultAugmented(fineImages, coarseScale, fineScale, augment, ctx=None):
     return AugmentedResult(fineImages, coarseScale, fineScale, augment)
 
 
+class PhotoResult:
+    """AugmentedResult for a set of whole photos (runtime.PhotoDataset, which holds the augmenter): every pull warps the picked
+    photos in photo coordinates into the face window, scales the window to fineScale with image.scale and computes coarse and diff
+    from that face, in one launch of fg_warp_faces.  The interface is AugmentedResult's: size, indices, gather_fields, gather,
+    [i] -> Example."""
+
+    def __init__(self, photos, coarseScale):
+        from .runtime import PhotoDataset, FgError
+        if not isinstance(photos, PhotoDataset):
+            raise FgError("PhotoResult: the set must be a runtime.PhotoDataset")
+        self.coarseScale, self.fineScale = int(coarseScale), photos.h
+        if not 1 <= self.coarseScale <= self.fineScale:
+            raise FgError("PhotoResult: coarse scale %d outside 1 .. %d" % (self.coarseScale, self.fineScale))
+        self.set, self.ctx = photos, photos.ctx
+
+    @property
+    def augment(self):
+        return self.set.augment
+
+    def size(self):
+        return self.set.size()
+
+    def __len__(self):
+        return self.size()
+
+    def indices(self, indices):
+        """host indices (range-checked, one upload) or a device int32 tensor -> device int32 [n], as DeviceDataset.indices"""
+        return self.set.indices(indices)
+
+    def gather_fields(self, indices, fields, layout="nhwc"):
+        """-> a tuple of device tensors [n][S][S][C] ("nhwc") or [n][C][S][S] ("nchw") in the order of `fields`, a subset of
+        ("fine", "coarse", "diff"): field f of the face of photo indices[j] under transform j.  One draw shared by all fields,
+        one launch."""
+        from .runtime import FgError
+        fields = tuple(fields)
+        if not fields or len(set(fields)) != len(fields) or any(f not in FIELDS for f in fields):
+            raise FgError("PhotoResult.gather_fields: fields must be a non-empty subset of %r, got %r" % (FIELDS, fields))
+        return self.set.gather_fields(indices, fields, coarse_scale=self.coarseScale, layout=layout)
+
+    def gather(self, indices, field, layout="nhwc"):
+        return self.gather_fields(indices, (field,), layout=layout)[0]
+
+    def __getitem__(self, i):
+        """Example(coarse, fine, diff) as host CHW tensors, all three under one fresh transform"""
+        i = int(i)
+        if i < 0 or i >= self.size():
+            raise IndexError("PhotoResult: index %d outside [0, %d)" % (i, self.size()))
+        coarse, fine, diff = self.gather_fields([i], ("coarse", "fine", "diff"), layout="nchw")
+        return Example(coarse[0].cpu(), fine[0].cpu(), diff[0].cpu())
+
+
+def toResultPhotos(photos, window_hw, coarseScale, fineScale, augment, ctx=None):
+    """toResult for training on faces cut from whole photos under fresh transforms: photos (host or device [N, C, H, W], any H and
+    W, or a runtime.PhotoDataset, which then carries window, fine scale and augmenter itself) is uploaded once and stays in HBM;
+    `augment`, an Augmenter whose out_hw is window_hw (or None: the central window, un-augmented), draws the transforms of every
+    pull -> PhotoResult."""
+    from .runtime import get_context, PhotoDataset, FgError
+    if isinstance(photos, PhotoDataset):
+        if augment is not None and augment is not photos.augment:
+            raise FgError("toResultPhotos: the PhotoDataset carries its own augmenter")
+        if photos.h != int(fineScale) or photos.window_hw != tuple(window_hw if not isinstance(window_hw, int) else (window_hw, window_hw)):
+            raise FgError("toResultPhotos: the PhotoDataset hands out %dx%d faces of a %dx%d window" % ((photos.h, photos.w) + photos.window_hw))
+        return PhotoResult(photos, coarseScale)
+    return PhotoResult(PhotoDataset(ctx or get_context(), photos, window_hw, int(fineScale), augment=augment), coarseScale)
+
+
 def toResultDevice(fine_nhwc, coarseScale, ctx=None):
     """The same step for a batch that already lives in HBM in the library's activation layout [N][S][S][C]: -> (coarse, diff) device
     tensors, the inputs of TrainerC2F.step_D / step_G."""

@@ -262,6 +262,50 @@ def warp_c2f(images, indices, fine_scale, coarse_scale, mats=None, gains=None, f
     return tuple(out[f] for f in fields)
 
 
+def warp_faces(photos, indices, window_hw, s, cs=0, mats=None, gains=None, fields=("fine",), set_layout="nchw", out_layout="nhwc",
+               fill="constant", out=None, ctx=None):
+    """The faces of photos[indices[j]] under mats[j] / gains[j] in one launch: include/facegen_hip.h fg_warp_faces.  The photos may
+    have any size: W = warp_images(.., out_hw=window_hw) in photo coordinates, fine = scale(W, s, s) and, with cs > 0, coarse =
+    scale(scale(fine, cs), s), diff = fine - coarse.  photos, indices, mats, gains, the layouts and fill as warp_images; fields:
+    the outputs wanted, a subset of ("fine", "coarse", "diff") without repeats (cs = 0: ("fine",) alone) -> a tuple of device
+    tensors [n][s][s][C] ("nhwc") or [n][C][s][s] in the order of fields; what is not asked for is not written.  out: a tensor
+    to write a single field into."""
+    ctx = ctx or get_context()
+    layouts, fills = {"nhwc": 0, "nchw": 1}, {"constant": 0, "edge": 1}
+    if set_layout not in layouts or out_layout not in layouts or fill not in fills:
+        raise ValueError("warp_faces: layouts are 'nhwc' / 'nchw', fill is 'constant' / 'edge'")
+    fields, s, cs = tuple(fields), int(s), int(cs)
+    allowed = ("fine", "coarse", "diff") if cs else ("fine",)
+    if not fields or len(set(fields)) != len(fields) or any(f not in allowed for f in fields):
+        raise ValueError("warp_faces: fields must be a non-empty subset of %r, got %r" % (allowed, fields))
+    if photos.dim() != 4 or photos.dtype != torch.float32 or not photos.is_contiguous():
+        raise ValueError("warp_faces: photos must be a contiguous float32 tensor of 4 dimensions")
+    if layouts[set_layout]:
+        N, C, H, W = photos.shape
+    else:
+        N, H, W, C = photos.shape
+    hw, ww = int(window_hw[0]), int(window_hw[1])
+    if indices.dtype != torch.int32 or indices.dim() != 1 or not indices.is_contiguous():
+        raise ValueError("warp_faces: indices must be a contiguous 1-d int32 tensor")
+    n = int(indices.numel())
+    for name, t, count in (("mats", mats, 6 * n), ("gains", gains, n)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != count):
+            raise ValueError("warp_faces: %s must be a contiguous float32 tensor of %d elements" % (name, count))
+    shape = (n, C, s, s) if layouts[out_layout] else (n, s, s, C)
+    if out is not None and (len(fields) != 1 or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * C * s * s):
+        raise ValueError("warp_faces: out takes a single field, a contiguous float32 tensor of %d elements" % (n * C * s * s))
+    for name, t in (("photos", photos), ("indices", indices), ("mats", mats), ("gains", gains), ("out", out)):
+        if t is not None and t.device != ctx.device:
+            raise ValueError("warp_faces: %s lives on %s, the context on %s" % (name, t.device, ctx.device))
+    res = {f: ctx.empty(*shape) if out is None else out.view(*shape) for f in fields}
+    P = lambda f: res[f].data_ptr() if f in res else None
+    if n:                                   # (an empty tensor has no address to hand over)
+        ctx.check(ctx.lib.fg_warp_faces(ctx.h, photos.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
+                                        None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n, hw, ww,
+                                        s, cs, P("fine"), P("coarse"), P("diff"), layouts[out_layout], fills[fill]))
+    return tuple(res[f] for f in fields)
+
+
 def draw_transforms(spec, n, src_hw, out_hw, seed, offset, ctx=None):
     """The transforms of n images drawn and assembled on the device: include/facegen_hip.h fg_draw_transforms.  spec: an
     _lib.AugmentSpec or a runtime.DeviceAugmenter (its spec(); out_hw may then be None, the augmenter's; its own offset stays where

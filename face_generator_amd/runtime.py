@@ -975,3 +975,108 @@ class DeviceAugmenter(Augmenter):
         """-> host float32 (mats [n][6], gains [n]): draw_device() read back (synchronises)"""
         both = self.draw_device(ctx or get_context(), n, src_hw).cpu().numpy()
         return both[:6 * n].reshape(n, 6).copy(), both[6 * n:].copy()
+
+
+class PhotoDataset:
+    """A training set of whole photos in HBM, [N][C][H][W] float32 (the reference's layout), that hands out faces the way the
+    reference makes them: dataset/generate_dataset.py:43-66 warps the 250 x 250 photo, so that rotations, shifts and zoom-out pull
+    in real background, cuts the 84 x 84 face window and resizes it, and dataset.lua:95 scales it with image.scale.  Every pull is
+    one launch of fg_warp_faces: the warp in photo coordinates into a window of window_hw, then image.scale to out_hw x out_hw.
+
+    The face window is the central one: photos are stored so that it is (LFW's window, rows 92 .. 175 and columns 83 .. 166, is
+    central in rows 18 .. 249 of its photos; cutting the set that way is the loader's business).  augment: an Augmenter or
+    DeviceAugmenter whose out_hw equals window_hw -- the transforms are drawn in window geometry, where the reference's 5 px of
+    translation are 5 px, against the photo size, so that the draw centres the window in the photo and mirrors about the photo:
+    the reference's flip, then warp, then crop for a horizontally centred window.  Without one a pull is the identity on the
+    central window, without gains.  One draw per pull (a host draw and one upload, or fg_draw_transforms); S.rng is never touched.
+
+    The dataset protocol is DeviceDataset's: size(), len(), ds[i] -> the host CHW face of the central window under the identity,
+    indices(), rows(), gather(); is_resident() is true for it."""
+
+    def __init__(self, ctx, photos, window_hw, out_hw, augment=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        x = torch.as_tensor(photos)
+        if x.dim() != 4 or x.shape[0] < 1:
+            raise FgError("PhotoDataset: photos must be [N][C][H][W] with N >= 1, got %s" % (tuple(x.shape),))
+        self.photos = x.to(dtype=torch.float32).to(ctx.device).contiguous()
+        self.n, self.c, self.photo_h, self.photo_w = (int(v) for v in self.photos.shape)
+        self.window_hw = (int(window_hw), int(window_hw)) if isinstance(window_hw, int) else (int(window_hw[0]), int(window_hw[1]))
+        sides = (out_hw, out_hw) if isinstance(out_hw, int) else tuple(out_hw)
+        if len(sides) != 2 or int(sides[0]) != int(sides[1]) or int(sides[0]) < 1:
+            raise FgError("PhotoDataset: the faces are square, out_hw = %s is not" % (out_hw,))
+        if min(self.window_hw) < 1:
+            raise FgError("PhotoDataset: window_hw must be positive, got %s" % (window_hw,))
+        self.h = self.w = int(sides[0])      # the images handed out, as DeviceDataset's h and w
+        self.set_augment(augment)
+        self._identity = None
+
+    def size(self):
+        return self.n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        i = int(i)
+        if i < 0 or i >= self.n:
+            raise IndexError("PhotoDataset: index %d outside [0, %d)" % (i, self.n))
+        return self.gather([i], layout="nchw", augment=False)[0].cpu()
+
+    def rows(self, lo, hi):
+        """the un-augmented faces lo .. hi-1 as a device tensor [hi - lo][C][h][w] (computed, one launch: the set holds photos)"""
+        return self.gather(torch.arange(lo, hi, dtype=torch.int32, device=self.ctx.device), layout="nchw", augment=False)
+
+    def indices(self, indices):
+        """host indices (range-checked here, one upload) or a device int32 tensor (used as it is) -> device int32 [n]"""
+        if isinstance(indices, torch.Tensor) and indices.device.type != "cpu":
+            if indices.dtype != torch.int32 or indices.dim() != 1:
+                raise FgError("PhotoDataset.gather: device indices must be a 1-d int32 tensor")
+            return indices.contiguous()
+        host = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
+        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= self.n):
+            raise IndexError("PhotoDataset.gather: index outside [0, %d)" % self.n)
+        return host.to(torch.int32).to(self.ctx.device)
+
+    def set_augment(self, augment):
+        """augment: an Augmenter or DeviceAugmenter whose out_hw is the window's, or None"""
+        if augment is not None and not isinstance(augment, Augmenter):
+            raise FgError("PhotoDataset: augment must be a runtime.Augmenter or None")
+        if augment is not None and tuple(augment.out_hw) != self.window_hw:
+            raise FgError("PhotoDataset: the augmenter draws for %dx%d images, the face window is %dx%d (the transforms are drawn in "
+                          "window geometry)" % (tuple(augment.out_hw) + self.window_hw))
+        self.augment = augment
+
+    def transforms(self, n, augment=True):
+        """-> (mats, gains, fill): device float32 [6n] and [n] (gains None without an augmenter) of one draw for n faces"""
+        aug = self.augment if augment else None
+        if aug is None:                     # the central window under the identity: equal rows, one buffer of the largest n so far
+            if self._identity is None or self._identity.numel() < 6 * n:
+                (hw, ww), hs, ws = self.window_hw, self.photo_h, self.photo_w
+                row = torch.tensor([1.0, 0.0, (ws - ww) / 2.0, 0.0, 1.0, (hs - hw) / 2.0], dtype=torch.float32)
+                self._identity = row.repeat(n).to(self.ctx.device)
+            return self._identity[:6 * n], None, "constant"
+        if isinstance(aug, DeviceAugmenter):
+            both = aug.draw_device(self.ctx, n, (self.photo_h, self.photo_w))   # drawn where they are used: no host draw, no upload
+        else:
+            mats, gains = aug.draw(n, (self.photo_h, self.photo_w))
+            both = torch.cat([torch.from_numpy(mats).reshape(-1), torch.from_numpy(gains)]).to(self.ctx.device)     # one transfer
+        return both[:6 * n], both[6 * n:], aug.fill
+
+    def gather_fields(self, indices, fields, coarse_scale=0, layout="nhwc", out=None, augment=True):
+        """-> a tuple of device tensors in the order of `fields` (ops.warp_faces), all of one draw: one launch of fg_warp_faces"""
+        from . import ops
+        if layout not in ("nhwc", "nchw"):
+            raise FgError("PhotoDataset.gather: layout must be 'nhwc' or 'nchw'")
+        idx = self.indices(indices)
+        n = int(idx.numel())
+        mats, gains, fill = self.transforms(n, augment) if n else (None, None, "constant")
+        try:
+            return ops.warp_faces(self.photos, idx, self.window_hw, self.h, coarse_scale, mats=mats, gains=gains, fields=fields,
+                                  set_layout="nchw", out_layout=layout, fill=fill, out=out, ctx=self.ctx)
+        except ValueError as e:
+            raise FgError("PhotoDataset.gather: %s" % e)
+
+    def gather(self, indices, layout="nhwc", out=None, augment=True):
+        """-> device [n][h][w][C] ("nhwc", what step_D / step_G and the nets take) or [n][C][h][w] ("nchw"): the face of photo
+        indices[j], under a fresh random transform with an augmenter set (and augment=True); repeated indices are legal"""
+        return self.gather_fields(indices, ("fine",), layout=layout, out=out, augment=augment)[0]

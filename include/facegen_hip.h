@@ -605,6 +605,44 @@ int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, i
                 const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout,
                 int fill);
 
+/* ---- a face under a fresh random transform, cut from a photo of any size: the reference's whole pipeline per batch
+ *      (dataset/generate_dataset.py:43-66 warps the 250 x 250 photo, cuts the 84 x 84 face window and resizes it; dataset.lua:95
+ *      scales that with image.scale), so that rotations, shifts and zoom-out pull in real background and no fill.  Gather + warp in
+ *      photo coordinates into a face window + image.scale to the face size + the coarse-to-fine fields, in one launch. ----
+ * set, n_set, c, set_layout, idx, n, out_layout, fill, mats, gains: as fg_warp_images.  The only differences: the set's images (the
+ *   photos) are hs x ws of ANY size -- a photo is never copied to LDS --, and the warp's output is the face window, hw x ww.
+ * Stage 1, the warp:  W = fg_warp_images(set, .., idx, mats, gains, n, W, hw, ww, channel-major, fill).  The coordinate arithmetic
+ *   and its operation order, the fp32 range test before any float-to-int conversion, the tap rules of both fills, the gain and the
+ *   clamp are the ones fg_warp_images states.  mats == NULL is the identity (hw == hs and ww == ws required), gains == NULL gain 1
+ *   without the clamp.  There is no window-origin argument: the matrix alone says where the window lies in the photo, as it does
+ *   for a 40 x 40 set cropped to 32 x 32.  A tap outside the photo addresses nothing.
+ * Stage 2, the scale:  F = image.scale(W, s, s) with the arithmetic of fg_scale_bilinear (the width pass nested in the height pass,
+ *   per output element); hw == ww == s is the copy.  fine = F.
+ * Stage 3, the coarse-to-fine fields, only with cs > 0:  coarse = image.scale(image.scale(F, cs, cs), s, s), diff = F - coarse, as
+ *   fg_c2f_coarse_diff computes them.  cs == 0: no coarse-to-fine fields; coarse and diff must be NULL and fine non-NULL.
+ * fine, coarse, diff: each n images of c x s x s device floats in out_layout, or NULL: not wanted, nothing is written for it.  With
+ *   cs > 0 at least one is non-NULL.  All four layout pairs.
+ * Bits: every written float equals, bit for bit, what fg_warp_images (to hw x ww), then fg_scale_bilinear (to s x s), then
+ *   fg_c2f_coarse_diff give through HBM, wherever that composition exists; where fg_warp_images refuses the source size, the float
+ *   the composition's stated arithmetic gives (every operation rounded on its own, no fused multiply-add).
+ * An idx[j] outside [0, n_set) reads nothing of `set` and fills image j of every requested output with quiet NaN (0x7fc00000);
+ *   repeated indices are legal.
+ * Nothing outside the requested outputs is written; nothing outside set, idx[0 .. n), mats[0 .. 6n), gains[0 .. n) is read.  A
+ *   photo's base offset is 64-bit, c * hs * ws < 2^31.  One launch on the context's stream, one block per face; no scratch
+ *   argument, no atomics, no synchronisation, stateless.  The window, the face and the cs x cs image live in LDS (the cs x cs image
+ *   takes the window's place), the intermediate batches of the composition never reach HBM.
+ * n == 0: FG_OK, nothing is launched.  NULL ctx / set / idx, a size < 1 (cs < 0), cs > s, n < 0, a layout or fill other than 0 / 1,
+ *   the NULL rules above broken, mats == NULL with differing sizes, a photo of 2^31 floats or more: FG_ERR_INVALID, nothing is
+ *   launched.  FG_ERR_UNSUPPORTED, the message names the entry, the sizes and the limit, if the window, the face, the cs x cs image
+ *   and the scale plans together do not fit the 160 KB of LDS of a compute unit:
+ *     4 * (roundup4(max(c*hw*ww, c*cs*cs)) + c*s*s) + 28 * (3*s + cs), rounded up to 16  >  163840 bytes
+ *   (roundup4: to a multiple of 4 floats; a scale plan is 28 bytes, one per coordinate of each of the four passes).
+ *   3 x 84 x 84 -> 64 -> 32 takes 140096 bytes.
+ * Alignment: 4 bytes are enough everywhere; photos and outputs are read and written 4 bytes at a time. */
+int fg_warp_faces(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx,
+                  const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff,
+                  int out_layout, int fill);
+
 /* ---- the random transforms of dataset/generate_dataset.py (:43-48 and its create_aug_matrices: flip, zoom, rotation, shear,
  *      translation, brightness) drawn, assembled into matrices and left on the device: the mats / gains of fg_warp_images and
  *      fg_warp_c2f for n images in one launch, no host arithmetic and no upload per batch. ----

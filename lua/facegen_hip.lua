@@ -150,6 +150,7 @@ int fg_nearest_update(fg_ctx* ctx, const float* queries, int q, const float* row
 int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int h, int w, int set_layout, const int* idx, int n, float* out, int out_layout);
 int fg_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill);
 int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill);
+int fg_warp_faces(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill);
 typedef struct fg_augment_spec { int hflip, vflip; int zoom_equal; double zoom_lo, zoom_hi; int rot_lo, rot_hi; int shear_lo, shear_hi; int tx_lo, tx_hi, ty_lo, ty_hi; double gain_lo, gain_hi; } fg_augment_spec;
 int fg_draw_transforms(fg_ctx* ctx, const fg_augment_spec* spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo, float* mats, float* gains);
 int fg_scale_bilinear(fg_ctx* ctx, const float* src, float* dst, int n, int c, int hs, int ws, int hd, int wd, int layout);
@@ -915,6 +916,84 @@ function M.augmentedResult(fineImages, coarseScale, fineScale, draw, fill)
     assert(coarseScale >= 1 and coarseScale <= fineScale, 'FG.augmentedResult: 1 <= coarseScale <= fineScale')
     local set = M.isDataset(fineImages) and fineImages or M.Dataset(fineImages)
     return setmetatable({set = set, coarseScale = coarseScale, fineScale = fineScale, draw = draw, fill = fill or 0}, Augmented)
+end
+-- fg_warp_faces: faces cut from whole photos under fresh transforms, the reference's pipeline per batch (dataset/generate_dataset.py
+-- :43-66 warps the 250 x 250 photo, cuts the 84 x 84 window and resizes it; dataset.lua:95 scales it): the warp in photo coordinates into
+-- a window of windowH x windowW, image.scale to s x s and, with cs > 0, coarse = scale(scale(fine, cs, cs), s, s), diff = fine - coarse,
+-- in one launch.  FG.photoDataset(photos, windowH, windowW, s, draw, fill): photos a host FloatTensor [N][C][H][W] of any H, W, uploaded
+-- once, stored so that the face window is the central one; draw(n, hs, ws) -> mats, gains as FG.augmenter(windowH, windowW, ..) hands it
+-- out (the transforms are drawn in window geometry, against the photo size), or nil: the central window under the identity.
+-- ds:size(), ds[i] -> the host CHW face of the central window (1-based), ds:gather(picks) -> device NHWC faces, one launch;
+-- ds:gatherFields(picks, fields, cs) -> the fields in that order, all under ONE draw; picks as FG.Dataset's gather takes them
+local Photos = {}
+Photos.__index = function(self, k)
+    if type(k) == 'number' then return Photos.get(self, k) end
+    return Photos[k]
+end
+function M.photoDataset(photos, windowH, windowW, s, draw, fill)
+    assert(photos:dim() == 4 and photos:size(1) >= 1, 'FG.photoDataset: [N][C][H][W] with N >= 1')
+    assert(windowH >= 1 and windowW >= 1 and s >= 1, 'FG.photoDataset: positive sizes')
+    assert(draw == nil or type(draw) == 'function', 'FG.photoDataset: draw(n, hs, ws) -> mats, gains')
+    return setmetatable({photos = M.DeviceTensor(photos:nElement()):copy(photos:float()), n = photos:size(1), c = photos:size(2),
+                         photoH = photos:size(3), photoW = photos:size(4), windowH = windowH, windowW = windowW, h = s, w = s, draw = draw,
+                         fill = fill or 0}, Photos)
+end
+function M.isPhotoDataset(x) return type(x) == 'table' and getmetatable(x) == Photos end
+function Photos:size() return self.n end
+-- the matrices of the central window under the identity for n faces -> mats (gains: nil)
+function Photos:identity(n)
+    local host = torch.FloatTensor(n, 6)
+    local row = {1, 0, (self.photoW - self.windowW) / 2, 0, 1, (self.photoH - self.windowH) / 2}
+    for k = 1, 6 do host:select(2, k):fill(row[k]) end
+    return M.DeviceTensor(6 * n):copy(host)
+end
+function Photos:gatherFields(picks, fields, cs, n, outLayout, augment)
+    local idx = picks
+    if not picks.ptr then
+        n = #picks
+        local zero = {}
+        for i = 1, n do
+            assert(picks[i] >= 1 and picks[i] <= self.n, 'FG.photoDataset:gatherFields: index out of range')
+            zero[i] = picks[i] - 1
+        end
+        idx = M.indexTensor(zero)
+    end
+    cs = cs or 0
+    local s, out = self.h, {}
+    for _, f in ipairs(fields) do
+        assert((f == 'fine' or ((f == 'coarse' or f == 'diff') and cs > 0)) and not out[f],
+               'FG.photoDataset:gatherFields: fine / coarse / diff, once each; coarse and diff with cs > 0')
+        out[f] = M.DeviceTensor(n * self.c * s * s)
+    end
+    local mats, gains
+    if self.draw and augment ~= false then mats, gains = self.draw(n, self.photoH, self.photoW) else mats = self:identity(n) end
+    check(C.fg_warp_faces(ctx, self.photos.ptr, self.n, self.c, self.photoH, self.photoW, 1, ffi.cast('const int*', idx.ptr), mats.ptr,
+                          gains and gains.ptr or nil, n, self.windowH, self.windowW, s, cs, out.fine and out.fine.ptr or nil,
+                          out.coarse and out.coarse.ptr or nil, out.diff and out.diff.ptr or nil, outLayout or 0, self.fill))
+    local res = {}
+    for i, f in ipairs(fields) do res[i] = out[f] end
+    return unpack(res)
+end
+function Photos:gather(picks, n, outLayout, augment) return (self:gatherFields(picks, {'fine'}, 0, n, outLayout, augment)) end
+function Photos:get(i)
+    assert(i >= 1 and i <= self.n, 'FG.photoDataset: index out of range')
+    local face = self:gather({i}, 1, 1, false)
+    local t = torch.FloatTensor(self.c, self.h, self.w)
+    check(C.fg_d2h(ctx, t:data(), face.ptr, t:nElement() * 4))
+    return t
+end
+-- dataset._toResult on faces cut from photos: FG.augmentedResult's interface (r:size(), r:gatherFields(picks, {'diff', 'coarse'}),
+-- r:gather(picks, field)) on an FG.photoDataset, or on photos with the arguments of one
+local PhotoResult = {}
+PhotoResult.__index = PhotoResult
+function PhotoResult:size() return self.set:size() end
+function PhotoResult:gatherFields(picks, fields, n, outLayout) return self.set:gatherFields(picks, fields, self.coarseScale, n, outLayout) end
+function PhotoResult:gather(picks, field, n, outLayout) return (self:gatherFields(picks, {field}, n, outLayout)) end
+function M.photoResult(photos, windowH, windowW, coarseScale, fineScale, draw, fill)
+    local set = M.isPhotoDataset(photos) and photos or M.photoDataset(photos, windowH, windowW, fineScale, draw, fill)
+    assert(set.h == fineScale, 'FG.photoResult: the photo set hands out faces of another size')
+    assert(coarseScale >= 1 and coarseScale <= fineScale, 'FG.photoResult: 1 <= coarseScale <= fineScale')
+    return setmetatable({set = set, coarseScale = coarseScale, fineScale = fineScale}, PhotoResult)
 end
 -- fg_draw_transforms: the transforms of n images drawn and assembled on the device -> mats (n * 6 floats, output pixel -> source pixel),
 -- gains (n floats) as DeviceTensors, what M.warpImages / ds:gatherWarped / ds:gatherWarpedC2F take.  spec: an fg_augment_spec cdata or a
