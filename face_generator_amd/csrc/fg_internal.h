@@ -91,6 +91,8 @@ static inline hipError_t fg_dev_alloc(void** p, size_t bytes) {
 }
 static inline void fg_dev_free(void* p) { if (g_fg_dry) free(p); else (void)hipFree(p); }
 #define FG_CHECK_LAUNCH(ctx) FG_HIP(ctx, hipGetLastError())
+// the grid of a grid-stride kernel over n units, bs per block: at most 4096 blocks (pointwise.hip, image.hip)
+#define FG_GRID(n, bs) dim3((unsigned)((((n) + (bs)-1) / (bs)) < 4096 ? (((n) + (bs)-1) / (bs)) : 4096))
 
 static inline int fg_round_up(int x, int m) { return (x + m - 1) / m * m; }
 static inline int fg_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
@@ -431,27 +433,6 @@ int fg_launch_colsum_final_thin(fg_ctx* ctx, const float* part, int nrb, float* 
 float* fg_defer_alloc(fg_ctx* ctx, long long floats);
 void fg_defer_push(fg_ctx* ctx, const float* part, int nrb, int C, float beta, float* out);
 int fg_defer_flush(fg_ctx* ctx);
-// image.scale (Torch7 `image`, bilinear): src [N][Hs][Ws][C] (nchw: [N][C][Hs][Ws]) -> dst at Hd x Wd; diff = sub_from - dst (optional)
-int fg_launch_scale_bilinear(fg_ctx*, const float* src, float* dst, int N, int C, int Hs, int Ws, int Hd, int Wd, int nchw,
-                             const float* sub_from, float* diff);
-// out[j] = clamp01(gains[j] * bilinear(set[idx[j]], mats[j])) (fg_warp_images): the source image of a block lives in LDS, so
-// c * hs * ws <= FG_WARP_MAX_FLOATS (64 KB, the dynamic LDS a launch gets without an attribute change); mats / gains may be null
-#define FG_WARP_MAX_FLOATS 16384
-int fg_launch_warp_images(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
-                          const float* gains, int n, float* out, int ho, int wo, int out_nchw, int edge);
-// fg_warp_c2f: the warp at s x s, then coarse = scale(scale(fine, cs), s) and diff = fine - coarse inside the block; fine / coarse /
-// diff may each be null (not written).  c * hs * ws and c * s * s <= FG_WARP_MAX_FLOATS: up to 135 KB of LDS, the limit raised per context
-int fg_launch_warp_c2f(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
-                       const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw, int edge);
-// fg_warp_faces: the warp of a photo of any size (taps from global memory) into an hw x ww window in LDS, the window scaled to s x s,
-// then fg_warp_c2f's fields (cs > 0).  fg_warp_faces_lds_bytes(..) <= FG_FACES_MAX_LDS, the whole LDS of a compute unit, is the
-// entry's check and the launch's dynamic LDS; FG_SCALE_PLAN_BYTES is sizeof(ScaleTerm) (asserted beside the kernel)
-#define FG_FACES_MAX_LDS 163840
-#define FG_SCALE_PLAN_BYTES 28
-size_t fg_warp_faces_lds_bytes(int c, int hw, int ww, int s, int cs);
-int fg_launch_warp_faces(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
-                         const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw,
-                         int edge);
 int fg_launch_zero_insert2(fg_ctx*, const float* g, float* out, int B, int H, int W, int C);   // g [B][H][W][C] -> out [B][2H][2W][C]
 
 // thin convolutions (3 <-> wide channels), NHWC, stride 1, "same" pad, odd k <= 7
@@ -588,8 +569,48 @@ struct RngSeg { float* out; long long n; uint64_t seed, offset; float lo, hi; in
 struct RngMulti { RngSeg seg[FG_RNG_MAX_SEGS]; int n; long long total_quads; };
 int fg_launch_rng_multi(fg_ctx*, RngMulti& m);   // fills q0 / total_quads; segment i == fg_launch_rng_*(seed_i, offset_i, ...)
 int fg_launch_rng_uniform(fg_ctx*, uint64_t seed, uint64_t offset, float* out, long long n, float lo, float hi);
-// fg_draw_transforms: image j takes the quads offset + 3j .. offset + 3j + 2 of the stream above; the spec is checked by the entry
-int fg_launch_draw_transforms(fg_ctx*, const fg_augment_spec& spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo,
-                              float* mats, float* gains);
 int fg_launch_rng_bernoulli(fg_ctx*, uint64_t seed, uint64_t offset, float* out, long long n, float keep_prob);
 int fg_launch_rng_normal(fg_ctx*, uint64_t seed, uint64_t offset, float* out, long long n, float mean, float std);
+// one quad of the stream: counter (c0 .. c3), key (k0, k1) -> four words (rng_kernel, rng_multi_kernel, draw_transforms_kernel)
+__device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                           uint32_t* out) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// ---------------------------------------------------------------------------------
+// the device data path (image.hip): image.scale, the warps of a resident image set, the draw of their transforms
+// ---------------------------------------------------------------------------------
+// the NaN of an image whose index lies outside the set (the gather of pointwise.hip, the warps)
+__device__ __forceinline__ float gi_nan() { return __int_as_float(0x7fc00000); }
+// image.scale (Torch7 `image`, bilinear): src [N][Hs][Ws][C] (nchw: [N][C][Hs][Ws]) -> dst at Hd x Wd; diff = sub_from - dst (optional)
+int fg_launch_scale_bilinear(fg_ctx*, const float* src, float* dst, int N, int C, int Hs, int Ws, int Hd, int Wd, int nchw,
+                             const float* sub_from, float* diff);
+// out[j] = clamp01(gains[j] * bilinear(set[idx[j]], mats[j])) (fg_warp_images): the source image of a block lives in LDS, so
+// c * hs * ws <= FG_WARP_MAX_FLOATS (64 KB, the dynamic LDS a launch gets without an attribute change); mats / gains may be null
+#define FG_WARP_MAX_FLOATS 16384
+int fg_launch_warp_images(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                          const float* gains, int n, float* out, int ho, int wo, int out_nchw, int edge);
+// fg_warp_c2f: the warp at s x s, then coarse = scale(scale(fine, cs), s) and diff = fine - coarse inside the block; fine / coarse /
+// diff may each be null (not written).  c * hs * ws and c * s * s <= FG_WARP_MAX_FLOATS: up to 135 KB of LDS, the limit raised per context
+int fg_launch_warp_c2f(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                       const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw, int edge);
+// fg_warp_faces: the warp of a photo of any size (taps from global memory) into an hw x ww window in LDS, the window scaled to s x s,
+// then fg_warp_c2f's fields (cs > 0).  fg_warp_faces_lds_bytes(..) <= FG_FACES_MAX_LDS, the whole LDS of a compute unit, is the
+// entry's check and the launch's dynamic LDS; FG_SCALE_PLAN_BYTES is sizeof(ScaleTerm) (asserted beside the kernel)
+#define FG_FACES_MAX_LDS 163840
+#define FG_SCALE_PLAN_BYTES 28
+size_t fg_warp_faces_lds_bytes(int c, int hw, int ww, int s, int cs);
+int fg_launch_warp_faces(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                         const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw,
+                         int edge);
+// fg_draw_transforms: image j takes the quads offset + 3j .. offset + 3j + 2 of the Philox stream; the spec is checked by the entry
+int fg_launch_draw_transforms(fg_ctx*, const fg_augment_spec& spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo,
+                              float* mats, float* gains);

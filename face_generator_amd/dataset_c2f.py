@@ -1,7 +1,7 @@
 """DATASET (coarse-to-fine): the `_toResult` step of dataset_c2f.lua:49-109 that sits directly in front of the c2f
 train step: coarse = fine scaled down to coarseScale and back up to fineScale, diff = fine - coarse, wrapped as an
 indexable result with .fine/.coarse/.diff.  `image.scale` runs on the device through the library's
-fg_c2f_coarse_diff (csrc/pointwise.hip scale_bilinear_kernel: the `image` package's bilinear algorithm bit for bit -- corner-aligned
+fg_c2f_coarse_diff (csrc/image.hip scale_bilinear_kernel: the `image` package's bilinear algorithm bit for bit -- corner-aligned
 linear interpolation up, fractional box mean down; the provenance note sits with the CPU restatement the parity tests use).  There is no CPU
 fallback: without the library / a GPU this raises like every other compute entry.
 JPEG loading (dataset_c2f.lua:111-215) is out of scope: the metric uses synthetic batches."""
@@ -98,7 +98,40 @@ def toResultResident(fineImages, coarseScale, fineScale, ctx=None, augment=None)
 FIELDS = ("fine", "coarse", "diff")
 
 
-class AugmentedResult:
+class _PerPullResult:
+    """what AugmentedResult and PhotoResult share: `set` is the resident set, gather_fields() the class's own pull; the messages
+    name the class"""
+
+    def size(self):
+        return self.set.size()
+
+    def __len__(self):
+        return self.size()
+
+    def indices(self, indices):
+        """host indices (range-checked, one upload) or a device int32 tensor -> device int32 [n], as DeviceDataset.indices"""
+        return self.set.indices(indices)
+
+    def _fields(self, fields):
+        from .runtime import FgError
+        fields = tuple(fields)
+        if not fields or len(set(fields)) != len(fields) or any(f not in FIELDS for f in fields):
+            raise FgError("%s.gather_fields: fields must be a non-empty subset of %r, got %r" % (type(self).__name__, FIELDS, fields))
+        return fields
+
+    def gather(self, indices, field, layout="nhwc"):
+        return self.gather_fields(indices, (field,), layout=layout)[0]
+
+    def __getitem__(self, i):
+        """Example(coarse, fine, diff) as host CHW tensors, all three under one fresh transform"""
+        i = int(i)
+        if i < 0 or i >= self.size():
+            raise IndexError("%s: index %d outside [0, %d)" % (type(self).__name__, i, self.size()))
+        coarse, fine, diff = self.gather_fields([i], ("coarse", "fine", "diff"), layout="nchw")
+        return Example(coarse[0].cpu(), fine[0].cpu(), diff[0].cpu())
+
+
+class AugmentedResult(_PerPullResult):
     """Result for training on freshly augmented faces: only the un-augmented fine set lives in HBM (a DeviceDataset without an
     augmenter, its images fineScale x fineScale or larger by a margin), and every pull computes the example of each picked face
     under a fresh random transform: warp to fineScale, scale down to coarseScale and back up, subtract, in one launch of
@@ -118,51 +151,24 @@ class AugmentedResult:
             raise FgError("AugmentedResult: coarse scale %d outside 1 .. %d" % (self.coarseScale, self.fineScale))
         self.set, self.augment, self.ctx = fine, augment, fine.ctx
 
-    def size(self):
-        return self.set.size()
-
-    def __len__(self):
-        return self.size()
-
-    def indices(self, indices):
-        """host indices (range-checked, one upload) or a device int32 tensor -> device int32 [n], as DeviceDataset.indices"""
-        return self.set.indices(indices)
-
     def gather_fields(self, indices, fields, layout="nhwc"):
         """-> a tuple of device tensors [n][S][S][C] ("nhwc") or [n][C][S][S] ("nchw") in the order of `fields`, a subset of
         ("fine", "coarse", "diff"): field f of dataset[indices[j]] under transform j.  One Augmenter.draw of n transforms shared
         by all fields, one upload, one launch; a runtime.DeviceAugmenter draws on the device instead (fg_draw_transforms: no
         host draw, no upload)."""
         from . import ops
-        from .runtime import DeviceAugmenter, FgError
+        from .runtime import FgError
         if layout not in ("nhwc", "nchw"):
             raise FgError("AugmentedResult.gather_fields: layout must be 'nhwc' or 'nchw'")
-        fields = tuple(fields)
-        if not fields or len(set(fields)) != len(fields) or any(f not in FIELDS for f in fields):
-            raise FgError("AugmentedResult.gather_fields: fields must be a non-empty subset of %r, got %r" % (FIELDS, fields))
+        fields = self._fields(fields)
         idx = self.indices(indices)
         n, ds, s = int(idx.numel()), self.set, self.fineScale
         if not n:
             shape = (0, s, s, ds.c) if layout == "nhwc" else (0, ds.c, s, s)
             return tuple(self.ctx.empty(*shape) for _ in fields)
-        if isinstance(self.augment, DeviceAugmenter):
-            both = self.augment.draw_device(self.ctx, n, (ds.h, ds.w))          # drawn where they are used: no host draw, no upload
-        else:
-            mats, gains = self.augment.draw(n, (ds.h, ds.w))
-            both = torch.cat([torch.from_numpy(mats).reshape(-1), torch.from_numpy(gains)]).to(self.ctx.device)     # one transfer
+        both = self.augment.draw_device(self.ctx, n, (ds.h, ds.w))
         return ops.warp_c2f(ds.images, idx, s, self.coarseScale, mats=both[:6 * n], gains=both[6 * n:], fields=fields, set_layout="nchw",
                             out_layout=layout, fill=self.augment.fill, ctx=self.ctx)
-
-    def gather(self, indices, field, layout="nhwc"):
-        return self.gather_fields(indices, (field,), layout=layout)[0]
-
-    def __getitem__(self, i):
-        """Example(coarse, fine, diff) as host CHW tensors, all three under one fresh transform"""
-        i = int(i)
-        if i < 0 or i >= self.size():
-            raise IndexError("AugmentedResult: index %d outside [0, %d)" % (i, self.size()))
-        coarse, fine, diff = self.gather_fields([i], ("coarse", "fine", "diff"), layout="nchw")
-        return Example(coarse[0].cpu(), fine[0].cpu(), diff[0].cpu())
 
 
 def toResultAugmented(fineImages, coarseScale, fineScale, augment, ctx=None):
@@ -181,7 +187,7 @@ def toResultAugmented(fineImages, coarseScale, fineScale, augment, ctx=None):
     return AugmentedResult(fineImages, coarseScale, fineScale, augment)
 
 
-class PhotoResult:
+class PhotoResult(_PerPullResult):
     """AugmentedResult for a set of whole photos (runtime.PhotoDataset, which holds the augmenter): every pull warps the picked
     photos in photo coordinates into the face window, scales the window to fineScale with image.scale and computes coarse and diff
     from that face, in one launch of fg_warp_faces.  The interface is AugmentedResult's: size, indices, gather_fields, gather,
@@ -200,36 +206,11 @@ class PhotoResult:
     def augment(self):
         return self.set.augment
 
-    def size(self):
-        return self.set.size()
-
-    def __len__(self):
-        return self.size()
-
-    def indices(self, indices):
-        """host indices (range-checked, one upload) or a device int32 tensor -> device int32 [n], as DeviceDataset.indices"""
-        return self.set.indices(indices)
-
     def gather_fields(self, indices, fields, layout="nhwc"):
         """-> a tuple of device tensors [n][S][S][C] ("nhwc") or [n][C][S][S] ("nchw") in the order of `fields`, a subset of
         ("fine", "coarse", "diff"): field f of the face of photo indices[j] under transform j.  One draw shared by all fields,
         one launch."""
-        from .runtime import FgError
-        fields = tuple(fields)
-        if not fields or len(set(fields)) != len(fields) or any(f not in FIELDS for f in fields):
-            raise FgError("PhotoResult.gather_fields: fields must be a non-empty subset of %r, got %r" % (FIELDS, fields))
-        return self.set.gather_fields(indices, fields, coarse_scale=self.coarseScale, layout=layout)
-
-    def gather(self, indices, field, layout="nhwc"):
-        return self.gather_fields(indices, (field,), layout=layout)[0]
-
-    def __getitem__(self, i):
-        """Example(coarse, fine, diff) as host CHW tensors, all three under one fresh transform"""
-        i = int(i)
-        if i < 0 or i >= self.size():
-            raise IndexError("PhotoResult: index %d outside [0, %d)" % (i, self.size()))
-        coarse, fine, diff = self.gather_fields([i], ("coarse", "fine", "diff"), layout="nchw")
-        return Example(coarse[0].cpu(), fine[0].cpu(), diff[0].cpu())
+        return self.set.gather_fields(indices, self._fields(fields), coarse_scale=self.coarseScale, layout=layout)
 
 
 def toResultPhotos(photos, window_hw, coarseScale, fineScale, augment, ctx=None):

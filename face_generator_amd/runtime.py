@@ -732,6 +732,18 @@ def is_resident(dataset):
     return not torch.is_tensor(dataset) and callable(getattr(dataset, "gather", None))
 
 
+def _device_indices(cls, ctx, indices, n_set):
+    """the indices() of the resident sets (cls: the class named in the messages)"""
+    if isinstance(indices, torch.Tensor) and indices.device.type != "cpu":
+        if indices.dtype != torch.int32 or indices.dim() != 1:
+            raise FgError("%s.gather: device indices must be a 1-d int32 tensor" % cls)
+        return indices.contiguous()
+    host = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= n_set):
+        raise IndexError("%s.gather: index outside [0, %d)" % (cls, n_set))
+    return host.to(torch.int32).to(ctx.device)
+
+
 class DeviceDataset:
     """A training set that lives in HBM (train.lua loads N_epoch images once per epoch, adversarial.lua:245 indexes them):
     [N][C][H][W] float32 on the device, the reference's layout and the order NearestSearch streams.  It keeps the reference's
@@ -771,14 +783,7 @@ class DeviceDataset:
 
     def indices(self, indices):
         """host indices (range-checked here, one upload) or a device int32 tensor (used as it is) -> device int32 [n]"""
-        if isinstance(indices, torch.Tensor) and indices.device.type != "cpu":
-            if indices.dtype != torch.int32 or indices.dim() != 1:
-                raise FgError("DeviceDataset.gather: device indices must be a 1-d int32 tensor")
-            return indices.contiguous()
-        host = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
-        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= self.n):
-            raise IndexError("DeviceDataset.gather: index outside [0, %d)" % self.n)
-        return host.to(torch.int32).to(self.ctx.device)
+        return _device_indices("DeviceDataset", self.ctx, indices, self.n)
 
     def set_augment(self, augment):
         """augment: an Augmenter (every gather() then returns its images under fresh random transforms) or None"""
@@ -818,11 +823,7 @@ class DeviceDataset:
         elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * self.c * ho * wo:
             raise FgError("DeviceDataset.gather: out must be a contiguous float32 tensor of %d elements" % (n * self.c * ho * wo))
         if n:
-            if isinstance(aug, DeviceAugmenter):
-                both = aug.draw_device(self.ctx, n, (self.h, self.w))           # drawn where they are used: no host draw, no upload
-            else:
-                mats, gains = aug.draw(n, (self.h, self.w))
-                both = torch.cat([torch.from_numpy(mats).reshape(-1), torch.from_numpy(gains)]).to(self.ctx.device)     # one transfer
+            both = aug.draw_device(self.ctx, n, (self.h, self.w))
             self.ctx.check(self.lib.fg_warp_images(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1, idx.data_ptr(),
                                                    both.data_ptr(), both.data_ptr() + 24 * n, n, out.data_ptr(), ho, wo,
                                                    0 if layout == "nhwc" else 1, aug.fill_code))
@@ -911,6 +912,12 @@ class Augmenter:
         picks = [self.draw_one() for _ in range(n)]
         mats = np.array([self.matrix(p, src_hw) for p in picks], dtype=np.float64).reshape(n, 6)
         return mats.astype(np.float32), np.array([p[8] for p in picks], dtype=np.float64).astype(np.float32)
+
+    def draw_device(self, ctx, n, src_hw):
+        """-> one device float32 tensor of 7n floats, the n matrices and then the n gains, where the warps read them: draw() and one
+        transfer (a DeviceAugmenter draws them there: no host draw, no upload)"""
+        mats, gains = self.draw(n, src_hw)
+        return torch.cat([torch.from_numpy(mats).reshape(-1), torch.from_numpy(gains)]).to(ctx.device)
 
 
 class DeviceAugmenter(Augmenter):
@@ -1028,14 +1035,7 @@ class PhotoDataset:
 
     def indices(self, indices):
         """host indices (range-checked here, one upload) or a device int32 tensor (used as it is) -> device int32 [n]"""
-        if isinstance(indices, torch.Tensor) and indices.device.type != "cpu":
-            if indices.dtype != torch.int32 or indices.dim() != 1:
-                raise FgError("PhotoDataset.gather: device indices must be a 1-d int32 tensor")
-            return indices.contiguous()
-        host = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
-        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= self.n):
-            raise IndexError("PhotoDataset.gather: index outside [0, %d)" % self.n)
-        return host.to(torch.int32).to(self.ctx.device)
+        return _device_indices("PhotoDataset", self.ctx, indices, self.n)
 
     def set_augment(self, augment):
         """augment: an Augmenter or DeviceAugmenter whose out_hw is the window's, or None"""
@@ -1055,11 +1055,7 @@ class PhotoDataset:
                 row = torch.tensor([1.0, 0.0, (ws - ww) / 2.0, 0.0, 1.0, (hs - hw) / 2.0], dtype=torch.float32)
                 self._identity = row.repeat(n).to(self.ctx.device)
             return self._identity[:6 * n], None, "constant"
-        if isinstance(aug, DeviceAugmenter):
-            both = aug.draw_device(self.ctx, n, (self.photo_h, self.photo_w))   # drawn where they are used: no host draw, no upload
-        else:
-            mats, gains = aug.draw(n, (self.photo_h, self.photo_w))
-            both = torch.cat([torch.from_numpy(mats).reshape(-1), torch.from_numpy(gains)]).to(self.ctx.device)     # one transfer
+        both = aug.draw_device(self.ctx, n, (self.photo_h, self.photo_w))
         return both[:6 * n], both[6 * n:], aug.fill
 
     def gather_fields(self, indices, fields, coarse_scale=0, layout="nhwc", out=None, augment=True):

@@ -187,6 +187,41 @@ def other_entries():
     ctx.check(lib.fg_parzen_min_dist(ctx.h, P(E(5, 300)), P(E(300)), P(E(300)), 5, 300, P(E(5)), P(E(1))))
     ctx.check(lib.fg_prof_clock_start(ctx.h, 1.0))
 run("OTHER_ENTRIES", "rank-grid-parzen-clock", other_entries)
+# the device data path (csrc/image.hip, and the gather of pointwise.hip), one job per case: planning-only calls of the public entries
+# at the smallest shapes that select each instance.  The GPU tests that compare them with a reference: test_gpu_dataset.py,
+# test_gpu_augment.py, test_gpu_augment_c2f.py, test_gpu_photo_faces.py, test_gpu_augment_draw.py
+def data_entries():
+    import ctypes
+    from face_generator_amd.runtime import DeviceAugmenter
+    E, P, PAIRS = torch.empty, (lambda t: t.data_ptr()), [(sl, ol) for sl in (1, 0) for ol in (1, 0)]
+    idx, mats, gains = torch.empty(4, dtype=torch.int32), E(4 * 6), E(4)
+    def gather():
+        for ol in (0, 1): ctx.check(lib.fg_gather_images(ctx.h, P(E(7, 3, 6, 8)), 7, 3, 6, 8, 1, P(idx), 4, P(E(4 * 3 * 6 * 8)), ol))
+    def gather_above_cap():     # the row copy at a shape of test_gpu_dataset.py::test_gather_above_the_grid_cap: one unit per image
+        n = 4096 + 259
+        ctx.check(lib.fg_gather_images(ctx.h, P(E(37, 3, 5, 7)), 37, 3, 5, 7, 1, P(torch.empty(n, dtype=torch.int32)), n, P(E(n * 3 * 5 * 7)), 1))
+    def warp_images():
+        for sl, ol in PAIRS:
+            ctx.check(lib.fg_warp_images(ctx.h, P(E(7 * 3 * 6 * 8)), 7, 3, 6, 8, sl, P(idx), P(mats), P(gains), 4, P(E(4 * 3 * 5 * 7)), 5, 7, ol, 0))
+    def warp_c2f(c, hs, s, cs, pairs):
+        o = [E(4 * c * s * s) for _ in range(3)]
+        for sl, ol in pairs:
+            ctx.check(lib.fg_warp_c2f(ctx.h, P(E(7 * c * hs * hs)), 7, c, hs, hs, sl, P(idx), P(mats), P(gains), 4, s, cs, P(o[0]), P(o[1]), P(o[2]), ol, 0))
+    def warp_faces(hs, ws, hw, ww, s, cs, pairs):
+        o = [E(4 * 3 * s * s) for _ in range(3)]
+        for sl, ol in pairs:
+            ctx.check(lib.fg_warp_faces(ctx.h, P(E(7 * 3 * hs * ws)), 7, 3, hs, ws, sl, P(idx), P(mats), P(gains), 4, hw, ww, s, cs, P(o[0]),
+                                        P(o[1]) if cs else None, P(o[2]) if cs else None, ol, 0))
+    def draw(n):
+        both = E(7 * n)
+        ctx.check(lib.fg_draw_transforms(ctx.h, ctypes.byref(DeviceAugmenter((32, 32)).spec()), 43, 0, n, 40, 40, 32, 32, P(both), P(both) + 24 * n))
+    return [("gather", gather), ("gather-above-cap", gather_above_cap), ("warp-images", warp_images), ("warp-c2f", lambda: warp_c2f(3, 6, 4, 2, PAIRS)),
+            ("warp-c2f-big", lambda: warp_c2f(3, 64, 64, 32, PAIRS[:1])),
+            ("warp-faces", lambda: (warp_faces(9, 11, 5, 6, 4, 2, PAIRS), warp_faces(9, 11, 5, 6, 4, 0, PAIRS[:1]))),
+            ("warp-faces-big", lambda: warp_faces(100, 100, 84, 84, 64, 32, PAIRS[:1])),
+            ("draw", lambda: draw(4)), ("draw-above-cap", lambda: draw(4096 * 256 + 259))]
+DATA_ENTRIES = data_entries()
+for name, f in DATA_ENTRIES: run("DATA_ENTRIES", name, f)
 """
 
 REPLAY = ENGINE + r"""
@@ -943,7 +978,8 @@ def strided_sweep(extra=()):
 
 @memo
 def pointwise_replay():
-    """CAP_CASES, BN_CASES, OPT_CASES and RNG_CASES of tests/test_gpu_pointwise_paths.py -> parsed jobs (one pass, "run")"""
+    """CAP_CASES, BN_CASES, OPT_CASES and RNG_CASES of tests/test_gpu_pointwise_paths.py, then OTHER_ENTRIES and DATA_ENTRIES (the
+    single-process entries and the device data path, called as their GPU tests call them) -> parsed jobs (one pass, "run")"""
     return parse_jobs(_run(POINTWISE_REPLAY))
 
 
@@ -1215,6 +1251,8 @@ if __name__ == "__main__":
     else:
         nets = net_launches()
         netk = {kernel_of(sig_of(l)[0]) for v in nets.values() for l in v}
+        # "the replay" as tests/test_dispatch_coverage_host.py takes it: every replayed list, not the conv / linear ones alone
+        covered = covered | all_sigs(strided_replay()) | all_sigs(pointwise_replay()) | all_sigs(net_replay()) | all_sigs(gan_replay())
         repk, swk = {kernel_of(s[0]) for s in covered}, {kernel_of(s[0]) for s in reach}
         for k, where in sorted(launch_sites().items()):
             st = "operator" if k in repk else "net-only" if k in netk else "SWEEP-ONLY" if k in swk else "?"

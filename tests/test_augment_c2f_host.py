@@ -138,35 +138,39 @@ def test_every_refusal_returns_its_code_names_the_entry_and_launches_nothing(chi
         assert sections[tag] == [], (tag, sections[tag])
 
 
-def test_an_empty_batch_launches_nothing_and_a_call_is_one_launch_of_the_scale_kernel(child):
+def test_an_empty_batch_launches_nothing_and_a_call_is_one_launch_of_the_c2f_kernel(child):
     sections, rcs = child
     assert rcs["n=0"][0][0] == 0 and sections["n=0"] == []
     assert all(rc == 0 for rc, _ in rcs["lay"]) and len(rcs["lay"]) == 16
     for tag in ("good", "no-mats", "no-gains", "limit", "limit-equal", "small-source", "gray", "only-coarse", "diff-coarse", "only-fine"):
-        assert rcs[tag][0][0] == 0 and len(sections[tag]) == 1 and sections[tag][0][0] == "scale_bilinear_kernel", (tag, rcs[tag], sections[tag])
+        assert rcs[tag][0][0] == 0 and len(sections[tag]) == 1 and sections[tag][0][0] == "warp_c2f_kernel", (tag, rcs[tag], sections[tag])
         assert sections[tag][0][1:5] == (4, 1, 1, 256), sections[tag]       # one block of 256 threads per image: the exact count
-    inst = {(1, 1): "<2, true, true>", (1, 0): "<2, true, false>", (0, 1): "<2, false, true>", (0, 0): "<2, false, false>"}
+    inst = {(1, 1): "<true, true>", (1, 0): "<true, false>", (0, 1): "<false, true>", (0, 0): "<false, false>"}
     for (sl, ol), text in inst.items():
         for off in (0, 1):
             for fill in (0, 1):
                 (name, gx, gy, gz, block, lds, line), = sections["lay-%d-%d-%d-%d" % (sl, ol, off, fill)]
-                assert name == "scale_bilinear_kernel" and text in line, line
+                assert name == "warp_c2f_kernel" and text in line, line
                 assert (gx, gy, gz, block) == (4, 1, 1, 256), line
                 assert lds == (3 * 6 * 8 + 3 * 4 * 4) * 4 + (4 + 2) * 28 + 8, line      # source image, fine image, s + cs plans, to 16 bytes
-    assert "<2, false, true>" in sections["limit"][0][-1]
-    assert "<2, true, true>" in sections["gray"][0][-1]                     # one channel: the two layouts are one order
+    assert "<false, true>" in sections["limit"][0][-1]
+    assert "<true, true>" in sections["gray"][0][-1]                        # one channel: the two layouts are one order
     # both images at the limit: 128 KB and the plans, within the 160 KB of a compute unit; cs == s and a source smaller than the
     # small image too
     for tag, plans in (("limit", 64 + 32), ("limit-equal", 64 + 64), ("small-source", 64 + 64)):
         assert sections[tag][0][5] == 2 * 65536 + plans * 28, sections[tag]
     assert max(s[0][5] for s in sections.values() if s) <= 163840
     # above the 64 KB a launch gets by default the limit of each instance is raised, once per context
-    src = open(os.path.join(ROOT, "face_generator_amd", "csrc", "pointwise.hip")).read()
+    src = open(os.path.join(ROOT, "face_generator_amd", "csrc", "image.hip")).read()
     launcher = src[src.index("int fg_launch_warp_c2f("):]
     launcher = launcher[:launcher.index("\n}\n")]
-    assert re.search(r"fg_attr_first\(ctx, &attr_key\)\)\s*\\?\s*FG_HIP\(ctx, hipFuncSetAttribute\(\(const void\*\)scale_bilinear_kernel<2, SN, ON>, "
+    assert re.search(r"fg_attr_first\(ctx, &attr_key\)\)\s*\\?\s*FG_HIP\(ctx, hipFuncSetAttribute\(\(const void\*\)warp_c2f_kernel<SN, ON>, "
                      r"hipFuncAttributeMaxDynamicSharedMemorySize", launcher), launcher
-    assert launcher.count("hipLaunchKernelGGL(") == 1 and "C2F(true, true)" in launcher and "C2F(false, false)" in launcher
+    # one launch site, expanded once per pair of layouts
+    assert launcher.count("hipLaunchKernelGGL(") == 1 and "FG_BY_LAYOUT(set_nchw, out_nchw, C2F)" in launcher
+    by_layout = src[src.index("#define FG_BY_LAYOUT("):]
+    by_layout = by_layout[:by_layout.index("\n//")]
+    assert all("LAUNCH(%s, %s);" % p in by_layout for p in (("true", "true"), ("true", "false"), ("false", "true"), ("false", "false"))), by_layout
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -18,7 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FG_ERR_INVALID = -1
 LAUNCH_RE = re.compile(r"^fg-launch (.*) grid=(\d+),(\d+),(\d+) block=(\d+) lds=(\d+)$")
-DRAW_KERNEL = "(rng_kernel<FG_RNG_TRANSFORMS>)"      # the launch-site text: the draw is a mode of the Philox kernel
+DRAW_KERNEL = "draw_transforms_kernel"               # the launch-site text
 SPEC_FIELDS = ("hflip", "vflip", "zoom_equal", "zoom_lo", "zoom_hi", "rot_lo", "rot_hi", "shear_lo", "shear_hi", "tx_lo", "tx_hi", "ty_lo", "ty_hi",
                "gain_lo", "gain_hi")
 # the reference's call (dataset/generate_dataset.py:43-48) at 32 x 32: round(5 * 32 / 84) = 2 px
@@ -445,8 +445,8 @@ def test_a_gather_with_a_device_augmenter_is_the_draw_kernel_and_one_warp_kernel
         elif cur is not None and l.startswith("fg-launch"):
             name = LAUNCH_RE.match(l).group(1)
             cur.append(name if name == DRAW_KERNEL else re.match(r"\(?\s*([A-Za-z_]\w*)", name).group(1))
-    assert sections["gather"] == [DRAW_KERNEL, "scale_bilinear_kernel"], sections
-    assert sections["fields"] == [DRAW_KERNEL, "scale_bilinear_kernel"], sections
+    assert sections["gather"] == [DRAW_KERNEL, "warp_images_kernel"], sections
+    assert sections["fields"] == [DRAW_KERNEL, "warp_c2f_kernel"], sections
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -237,22 +237,22 @@ def test_every_refusal_returns_its_code_names_the_entry_and_launches_nothing(chi
     assert rcs["null-ctx"][0][0] == FG_ERR_INVALID and sections["null-ctx"] == []
 
 
-def test_an_empty_batch_launches_nothing_and_a_warp_is_one_launch_of_the_scale_kernel(child):
+def test_an_empty_batch_launches_nothing_and_a_warp_is_one_launch_of_the_warp_kernel(child):
     sections, rcs = child
     assert rcs["n=0"][0][0] == 0 and sections["n=0"] == []
     assert all(rc == 0 for rc, _ in rcs["lay"]) and len(rcs["lay"]) == 16
     for tag in ("good", "no-mats", "no-gains", "lds-16384", "gray"):
-        assert rcs[tag][0][0] == 0 and len(sections[tag]) == 1 and sections[tag][0][0] == "scale_bilinear_kernel", (tag, rcs[tag], sections[tag])
+        assert rcs[tag][0][0] == 0 and len(sections[tag]) == 1 and sections[tag][0][0] == "warp_images_kernel", (tag, rcs[tag], sections[tag])
     assert sections["lds-16384"][0][5] == 65536          # the 64 KB a launch gets without an attribute change
-    inst = {(1, 1): "<1, true, true>", (1, 0): "<1, true, false>", (0, 1): "<1, false, true>", (0, 0): "<1, false, false>"}
+    inst = {(1, 1): "<true, true>", (1, 0): "<true, false>", (0, 1): "<false, true>", (0, 0): "<false, false>"}
     for (sl, ol), text in inst.items():
         for off in (0, 1):
             for fill in (0, 1):
                 (name, gx, gy, gz, block, lds, line), = sections["lay-%d-%d-%d-%d" % (sl, ol, off, fill)]
-                assert name == "scale_bilinear_kernel" and text in line, line
+                assert name == "warp_images_kernel" and text in line, line
                 assert (gx, gy, gz, block) == (4, 1, 1, 256), line          # one block per output image: the exact count
                 assert lds == 3 * 6 * 8 * 4, line                           # the source image
-    assert "<1, true, true>" in sections["gray"][0][-1]                    # one channel: the two layouts are one order
+    assert "<true, true>" in sections["gray"][0][-1]                       # one channel: the two layouts are one order
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -232,16 +232,19 @@ def test_nets_with_reclassified_layers_plan_and_run_forward_and_backward():
 def test_no_launch_asks_for_more_lds_than_the_launcher_arranged(audit):
     """a launch above 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize set on that kernel, and nothing above
     160 KB exists -- a planning-only run returns FG_OK for such a launch, a device refuses it.  (The check is by kernel NAME: a
-    template one of whose instances raises the limit passes for all its instances.)"""
+    template one of whose instances raises the limit passes for all its instances.)  The pointwise replay is walked too: its
+    DATA_ENTRIES hold the two launches of the data path above 64 KB, warp-c2f-big and warp-faces-big."""
     src = "".join(open(os.path.join(A.CSRC, f)).read() for f in sorted(os.listdir(A.CSRC)) if f.endswith(".hip"))
     raised = set(re.findall(r"hipFuncSetAttribute\(\(const void\*\)\s*([A-Za-z_]\w*)", src))
     bad = {}
-    for j in audit["sweep"] + audit["replay"]:
+    for j in audit["sweep"] + audit["replay"] + audit["pointwise"]:
         for v in j["sigs"].values():
             for s in v:
                 if s[2] > LDS_MAX or (s[2] > LDS_PLAIN and A.kernel_of(s[0]) not in raised):
                     bad.setdefault(s, j["shape"])
     assert not bad, bad
+    big = {j["case"]: max(s[2] for s in j["sigs"]["run"]) for j in audit["pointwise"] if j["list"] == "DATA_ENTRIES"}
+    assert big["warp-c2f-big"] > LDS_PLAIN and big["warp-faces-big"] == 140096, big
 
 
 def measure_only_sites():

@@ -1,4 +1,4 @@
-"""GPU: fg_scale_bilinear / fg_c2f_coarse_diff (csrc/pointwise.hip scale_bilinear_kernel) against the restatement of Torch7
+"""GPU: fg_scale_bilinear / fg_c2f_coarse_diff (csrc/image.hip scale_bilinear_kernel) against the restatement of Torch7
 `image.scale` (oracle/image_scale.py) -- BIT-FOR-BIT (the kernel performs the same IEEE float operations in the same order), in both
 layouts, at the reference's sizes (dataset_c2f.lua:53-61: 64 -> 32 -> 64) and at ragged ones, and against the committed known-answer
 vectors; dataset_c2f.toResult / toResultDevice (the host mirror of dataset._toResult) ride on it."""

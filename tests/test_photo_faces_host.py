@@ -259,30 +259,34 @@ def test_an_empty_batch_launches_nothing_and_a_call_is_one_launch_of_one_block_p
     assert all(rc == 0 for rc, _ in rcs["lay"]) and len(rcs["lay"]) == 16
     for tag in ("good", "no-mats", "no-gains", "just-fits", "lfw-64", "lfw-32", "photo-big", "old-limit", "gray", "only-coarse", "diff-coarse",
                 "only-fine"):
-        assert rcs[tag][0][0] == 0 and len(sections[tag]) == 1 and sections[tag][0][0] == "scale_bilinear_kernel", (tag, rcs[tag], sections[tag])
+        assert rcs[tag][0][0] == 0 and len(sections[tag]) == 1 and sections[tag][0][0] == "warp_faces_kernel", (tag, rcs[tag], sections[tag])
         assert sections[tag][0][1:5] == (4, 1, 1, 256), sections[tag]       # one block of 256 threads per face: the exact count
         assert sections[tag][0][5] <= 163840, sections[tag]
-    inst = {(1, 1): "<3, true, true>", (1, 0): "<3, true, false>", (0, 1): "<3, false, true>", (0, 0): "<3, false, false>"}
+    inst = {(1, 1): "<true, true>", (1, 0): "<true, false>", (0, 1): "<false, true>", (0, 0): "<false, false>"}
     for (sl, ol), text in inst.items():
         for off in (0, 1):
             for fill in (0, 1):
                 (name, gx, gy, gz, block, lds, line), = sections["lay-%d-%d-%d-%d" % (sl, ol, off, fill)]
-                assert name == "scale_bilinear_kernel" and text in line, line
+                assert name == "warp_faces_kernel" and text in line, line
                 assert (gx, gy, gz, block) == (4, 1, 1, 256), line
                 assert lds == lds_bytes(3, 6, 8, 4, 2) == (3 * 6 * 8 + 3 * 4 * 4) * 4 + (3 * 4 + 2) * 28 + 8, line
-    assert "<3, false, true>" in sections["old-limit"][0][-1]
-    assert "<3, true, true>" in sections["gray"][0][-1]                        # one channel: the two layouts are one order
+    assert "<false, true>" in sections["old-limit"][0][-1]
+    assert "<true, true>" in sections["gray"][0][-1]                           # one channel: the two layouts are one order
     assert sections["lfw-64"][0][5] == 140096 and sections["lfw-32"][0][5] == lds_bytes(3, 84, 84, 32, 0)
     assert sections["just-fits"][0][5] == lds_bytes(1, 1, 35296, 64, 32) <= 163840
     assert sections["no-mats"][0][5] == lds_bytes(3, 30, 40, 4, 2)          # the window is the photo
     # above the 64 KB a launch gets by default the limit of each instance is raised, once per context
     import re
-    src = open(os.path.join(ROOT, "face_generator_amd", "csrc", "pointwise.hip")).read()
+    src = open(os.path.join(ROOT, "face_generator_amd", "csrc", "image.hip")).read()
     launcher = src[src.index("int fg_launch_warp_faces("):]
     launcher = launcher[:launcher.index("\n}\n")]
-    assert re.search(r"fg_attr_first\(ctx, &attr_key\)\)\s*\\?\s*FG_HIP\(ctx, hipFuncSetAttribute\(\(const void\*\)scale_bilinear_kernel<3, SN, ON>,\s*"
+    assert re.search(r"fg_attr_first\(ctx, &attr_key\)\)\s*\\?\s*FG_HIP\(ctx, hipFuncSetAttribute\(\(const void\*\)warp_faces_kernel<SN, ON>,\s*"
                      r"hipFuncAttributeMaxDynamicSharedMemorySize", launcher), launcher
-    assert launcher.count("hipLaunchKernelGGL(") == 1 and "FACES(true, true)" in launcher and "FACES(false, false)" in launcher
+    # one launch site, expanded once per pair of layouts
+    assert launcher.count("hipLaunchKernelGGL(") == 1 and "FG_BY_LAYOUT(set_nchw, out_nchw, FACES)" in launcher
+    by_layout = src[src.index("#define FG_BY_LAYOUT("):]
+    by_layout = by_layout[:by_layout.index("\n//")]
+    assert all("LAUNCH(%s, %s);" % p in by_layout for p in (("true", "true"), ("true", "false"), ("false", "true"), ("false", "false"))), by_layout
 
 
 def test_the_siblings_still_refuse_sources_above_their_limit(plan_ctx):
