@@ -43,6 +43,7 @@ _CTYPES = [
     (r"^char\*$", ctypes.c_char_p),
     (r"^long long\*$", ctypes.POINTER(ctypes.c_longlong)),
     (r"^(const )?double\*$", ctypes.c_void_p),
+    (r"^const uint8_t\*$", ctypes.c_void_p),
     (r"^(const )?(fg_ctx|fg_net|fg_comm|fg_gan|fg_sampler|void|float|int)\*$", ctypes.c_void_p),
     (r"^int$", ctypes.c_int),
     (r"^long long$", ctypes.c_longlong),

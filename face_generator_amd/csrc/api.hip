@@ -270,71 +270,111 @@ int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int 
     if (n == 0) return FG_OK;
     return fg_launch_gather_images(ctx, set, n_set, c, h * w, set_layout, idx, n, out, out_layout);
 }
-int fg_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
-                   const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill) {
-    NEED(ctx, ctx, "null ctx");
+// The checks of the three warps, shared by the fp32 entry and its _u8 sibling (`who`: the entry a message names; `set` is only tested
+// against NULL).  FG_OK: launch, unless n == 0
+static int warp_images_check(fg_ctx* ctx, const char* who, const void* set, long long n_set, int c, int hs, int ws, int set_layout,
+                             const int* idx, const float* mats, int n, const float* out, int ho, int wo, int out_layout, int fill) {
     if (!set || !idx || !out || n_set < 1 || c < 1 || hs < 1 || ws < 1 || ho < 1 || wo < 1 || n < 0 || (set_layout != 0 && set_layout != 1) ||
         (out_layout != 0 && out_layout != 1) || (fill != 0 && fill != 1))
-        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_images: bad argument (n_set=%lld c=%d %dx%d -> %dx%d n=%d layouts %d -> %d fill=%d)", n_set, c,
+        return fg_set_err(ctx, FG_ERR_INVALID, "%s: bad argument (n_set=%lld c=%d %dx%d -> %dx%d n=%d layouts %d -> %d fill=%d)", who, n_set, c,
                           hs, ws, ho, wo, n, set_layout, out_layout, fill);
     if (!mats && (ho != hs || wo != ws))
-        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_images: without matrices the batch has the set's size, not %dx%d -> %dx%d", hs, ws, ho, wo);
+        return fg_set_err(ctx, FG_ERR_INVALID, "%s: without matrices the batch has the set's size, not %dx%d -> %dx%d", who, hs, ws, ho, wo);
     // (products of two ints at a time: three could pass 2^63)
     if ((long long)c * hs > FG_WARP_MAX_FLOATS || (long long)c * hs * ws > FG_WARP_MAX_FLOATS)
-        return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "fg_warp_images: a source image of %d x %d x %d = %.0f floats is above the %d that fit in LDS", c,
+        return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "%s: a source image of %d x %d x %d = %.0f floats is above the %d that fit in LDS", who, c,
                           hs, ws, (double)c * hs * ws, FG_WARP_MAX_FLOATS);
     if ((long long)c * ho >= (1LL << 31) || (long long)c * ho * wo >= (1LL << 31))
-        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_images: an output image of %d x %d x %d floats is 2^31 floats or more", c, ho, wo);
-    if (n == 0) return FG_OK;
-    return fg_launch_warp_images(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, out, ho, wo, out_layout, fill);
+        return fg_set_err(ctx, FG_ERR_INVALID, "%s: an output image of %d x %d x %d floats is 2^31 floats or more", who, c, ho, wo);
+    return FG_OK;
 }
-int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
-                const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill) {
-    NEED(ctx, ctx, "null ctx");
+static int warp_c2f_check(fg_ctx* ctx, const char* who, const void* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx,
+                          const float* mats, int n, int s, int cs, const float* fine, const float* coarse, const float* diff, int out_layout,
+                          int fill) {
     if (!set || !idx || (!fine && !coarse && !diff) || n_set < 1 || c < 1 || hs < 1 || ws < 1 || s < 1 || cs < 1 || cs > s || n < 0 ||
         (set_layout != 0 && set_layout != 1) || (out_layout != 0 && out_layout != 1) || (fill != 0 && fill != 1))
-        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_c2f: bad argument (n_set=%lld c=%d %dx%d -> %dx%d, coarse %dx%d, n=%d layouts %d -> %d fill=%d%s)",
+        return fg_set_err(ctx, FG_ERR_INVALID, "%s: bad argument (n_set=%lld c=%d %dx%d -> %dx%d, coarse %dx%d, n=%d layouts %d -> %d fill=%d%s)", who,
                           n_set, c, hs, ws, s, s, cs, cs, n, set_layout, out_layout, fill, !fine && !coarse && !diff ? ", no output" : "");
     if (!mats && (hs != s || ws != s))
-        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_c2f: without matrices the batch has the set's size, not %dx%d -> %dx%d", hs, ws, s, s);
+        return fg_set_err(ctx, FG_ERR_INVALID, "%s: without matrices the batch has the set's size, not %dx%d -> %dx%d", who, hs, ws, s, s);
     // (products of two ints at a time: three could pass 2^63)
     if ((long long)c * hs > FG_WARP_MAX_FLOATS || (long long)c * hs * ws > FG_WARP_MAX_FLOATS)
-        return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "fg_warp_c2f: a source image of %d x %d x %d = %.0f floats is above the %d that fit in LDS", c, hs,
+        return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "%s: a source image of %d x %d x %d = %.0f floats is above the %d that fit in LDS", who, c, hs,
                           ws, (double)c * hs * ws, FG_WARP_MAX_FLOATS);
     if ((long long)c * s > FG_WARP_MAX_FLOATS || (long long)c * s * s > FG_WARP_MAX_FLOATS)
-        return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "fg_warp_c2f: a fine image of %d x %d x %d = %.0f floats is above the %d that fit in LDS", c, s, s,
+        return fg_set_err(ctx, FG_ERR_UNSUPPORTED, "%s: a fine image of %d x %d x %d = %.0f floats is above the %d that fit in LDS", who, c, s, s,
                           (double)c * s * s, FG_WARP_MAX_FLOATS);
-    if (n == 0) return FG_OK;
-    return fg_launch_warp_c2f(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, s, cs, fine, coarse, diff, out_layout, fill);
+    return FG_OK;
 }
-int fg_warp_faces(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
-                  const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill) {
-    NEED(ctx, ctx, "null ctx");
+static int warp_faces_check(fg_ctx* ctx, const char* who, const void* set, long long n_set, int c, int hs, int ws, int set_layout,
+                            const int* idx, const float* mats, int n, int hw, int ww, int s, int cs, const float* fine, const float* coarse,
+                            const float* diff, int out_layout, int fill) {
     const bool outputs = cs > 0 ? fine || coarse || diff : fine && !coarse && !diff;
     if (!set || !idx || !outputs || n_set < 1 || c < 1 || hs < 1 || ws < 1 || hw < 1 || ww < 1 || s < 1 || cs < 0 || cs > s || n < 0 ||
         (set_layout != 0 && set_layout != 1) || (out_layout != 0 && out_layout != 1) || (fill != 0 && fill != 1))
         return fg_set_err(ctx, FG_ERR_INVALID,
-                          "fg_warp_faces: bad argument (n_set=%lld c=%d %dx%d -> window %dx%d -> %dx%d, coarse %dx%d, n=%d layouts %d -> %d fill=%d%s)",
+                          "%s: bad argument (n_set=%lld c=%d %dx%d -> window %dx%d -> %dx%d, coarse %dx%d, n=%d layouts %d -> %d fill=%d%s)", who,
                           n_set, c, hs, ws, hw, ww, s, s, cs, cs, n, set_layout, out_layout, fill,
                           outputs ? "" : cs > 0 ? ", no output" : ", cs = 0 takes fine alone");
     if (!mats && (hw != hs || ww != ws))
-        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_faces: without matrices the window has the photo's size, not %dx%d -> %dx%d", hs, ws, hw, ww);
+        return fg_set_err(ctx, FG_ERR_INVALID, "%s: without matrices the window has the photo's size, not %dx%d -> %dx%d", who, hs, ws, hw, ww);
     // (products of two ints at a time: three could pass 2^63)
     if ((long long)c * hs >= (1LL << 31) || (long long)c * hs * ws >= (1LL << 31))
-        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_faces: a photo of %d x %d x %d floats is 2^31 floats or more", c, hs, ws);
+        return fg_set_err(ctx, FG_ERR_INVALID, "%s: a photo of %d x %d x %d floats is 2^31 floats or more", who, c, hs, ws);
     const long long lim = FG_FACES_MAX_LDS / 4;
     const bool small = (long long)c * hw <= lim && (long long)c * hw * ww <= lim && (long long)c * s <= lim && (long long)c * s * s <= lim;
     if (!small)                             // (one of the images alone is above the limit; the sum below could pass 2^63)
         return fg_set_err(ctx, FG_ERR_UNSUPPORTED,
-                          "fg_warp_faces: a window of %d x %d x %d or a face of %d x %d x %d floats alone is above the %d bytes of LDS of a "
-                          "compute unit", c, hw, ww, c, s, s, FG_FACES_MAX_LDS);
+                          "%s: a window of %d x %d x %d or a face of %d x %d x %d floats alone is above the %d bytes of LDS of a "
+                          "compute unit", who, c, hw, ww, c, s, s, FG_FACES_MAX_LDS);
     if (fg_warp_faces_lds_bytes(c, hw, ww, s, cs) > FG_FACES_MAX_LDS)
         return fg_set_err(ctx, FG_ERR_UNSUPPORTED,
-                          "fg_warp_faces: a window of %d x %d x %d, a face of %d x %d x %d and a coarse image of %d x %d x %d floats with their "
-                          "%lld scale plans take %lld bytes, above the %d bytes of LDS of a compute unit",
+                          "%s: a window of %d x %d x %d, a face of %d x %d x %d and a coarse image of %d x %d x %d floats with their "
+                          "%lld scale plans take %lld bytes, above the %d bytes of LDS of a compute unit", who,
                           c, hw, ww, c, s, s, c, cs, cs, 3LL * s + cs, (long long)fg_warp_faces_lds_bytes(c, hw, ww, s, cs), FG_FACES_MAX_LDS);
-    if (n == 0) return FG_OK;
+    return FG_OK;
+}
+int fg_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                   const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    const int r = warp_images_check(ctx, "fg_warp_images", set, n_set, c, hs, ws, set_layout, idx, mats, n, out, ho, wo, out_layout, fill);
+    if (r != FG_OK || n == 0) return r;
+    return fg_launch_warp_images(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, out, ho, wo, out_layout, fill);
+}
+int fg_warp_images_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                      const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    const int r = warp_images_check(ctx, "fg_warp_images_u8", set, n_set, c, hs, ws, set_layout, idx, mats, n, out, ho, wo, out_layout, fill);
+    if (r != FG_OK || n == 0) return r;
+    return fg_launch_warp_images_u8(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, out, ho, wo, out_layout, fill);
+}
+int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    const int r = warp_c2f_check(ctx, "fg_warp_c2f", set, n_set, c, hs, ws, set_layout, idx, mats, n, s, cs, fine, coarse, diff, out_layout, fill);
+    if (r != FG_OK || n == 0) return r;
+    return fg_launch_warp_c2f(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, s, cs, fine, coarse, diff, out_layout, fill);
+}
+int fg_warp_c2f_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                   const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    const int r = warp_c2f_check(ctx, "fg_warp_c2f_u8", set, n_set, c, hs, ws, set_layout, idx, mats, n, s, cs, fine, coarse, diff, out_layout, fill);
+    if (r != FG_OK || n == 0) return r;
+    return fg_launch_warp_c2f_u8(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, s, cs, fine, coarse, diff, out_layout, fill);
+}
+int fg_warp_faces(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                  const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    const int r = warp_faces_check(ctx, "fg_warp_faces", set, n_set, c, hs, ws, set_layout, idx, mats, n, hw, ww, s, cs, fine, coarse, diff, out_layout, fill);
+    if (r != FG_OK || n == 0) return r;
     return fg_launch_warp_faces(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, hw, ww, s, cs, fine, coarse, diff, out_layout, fill);
+}
+int fg_warp_faces_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                     const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    const int r = warp_faces_check(ctx, "fg_warp_faces_u8", set, n_set, c, hs, ws, set_layout, idx, mats, n, hw, ww, s, cs, fine, coarse, diff, out_layout, fill);
+    if (r != FG_OK || n == 0) return r;
+    return fg_launch_warp_faces_u8(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, hw, ww, s, cs, fine, coarse, diff, out_layout, fill);
 }
 // what is wrong with a spec, or NULL: every range lo <= hi, the integer ones at most 2^31 values wide (the pick is a 32 x 32 bit product)
 static const char* augment_spec_fault(const fg_augment_spec& s) {

@@ -611,6 +611,16 @@ size_t fg_warp_faces_lds_bytes(int c, int hw, int ww, int s, int cs);
 int fg_launch_warp_faces(fg_ctx*, const float* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx, const float* mats,
                          const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw,
                          int edge);
+// the _u8 entries: the three warps on a set held as 8-bit pixels of value b / 255, decoded where global memory is read (the copy into
+// LDS, the taps of the faces kernel).  Grids, blocks, LDS sizes and limits are the fp32 launchers'; any alignment of `set`
+int fg_launch_warp_images_u8(fg_ctx*, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx,
+                             const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_nchw, int edge);
+int fg_launch_warp_c2f_u8(fg_ctx*, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx,
+                          const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw,
+                          int edge);
+int fg_launch_warp_faces_u8(fg_ctx*, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx,
+                            const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse,
+                            float* diff, int out_nchw, int edge);
 // fg_draw_transforms: image j takes the quads offset + 3j .. offset + 3j + 2 of the Philox stream; the spec is checked by the entry
 int fg_launch_draw_transforms(fg_ctx*, const fg_augment_spec& spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo,
                               float* mats, float* gains);

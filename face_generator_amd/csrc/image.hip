@@ -1,5 +1,6 @@
 // The device data path for gfx950 (wave = 64): image.scale, the warps of an HBM-resident image set (fg_warp_images, fg_warp_c2f,
-// fg_warp_faces) and the draw of their transforms (fg_draw_transforms).  One kernel name per entry.  The gather (fg_gather_images)
+// fg_warp_faces; their _u8 siblings on a set of 8-bit pixels are instances of the same kernels) and the draw of their transforms
+// (fg_draw_transforms).  One kernel name per entry.  The gather (fg_gather_images)
 // is in pointwise.hip: it shares its tile code with the layout kernels of the step path.
 // Reference semantics: include/facegen_hip.h (dataset_c2f.lua:53-61, dataset.lua:95, generate_dataset.py).
 #include "fg_internal.h"
@@ -140,6 +141,71 @@ __device__ __forceinline__ void wi_load(const float* __restrict__ s, float* __re
         }
     }
 }
+// A set held as 8-bit pixels (the _u8 entries, PIX = uint8_t): the value of a byte b is b / 255 by a true division, the correctly
+// rounded fp32 quotient the host loaders produce (b * (1 / 255) gives another float for 126 of the 256 bytes).  A pixel is decoded
+// where it leaves global memory and nowhere else, so everything behind the decode is the fp32 code on the same floats
+__device__ __forceinline__ float wi_pix(float v) { return v; }
+__device__ __forceinline__ float wi_pix(uint8_t b) { return (float)b / 255.0f; }
+__device__ __forceinline__ float wi_pix(uint32_t b) { return (float)b / 255.0f; }       // a byte in a register of its own
+// The four taps of a channel read straight from global memory (wi_warp<.., LDS_IMG = false>): wi_raw is a tap as it is read, a float
+// or a byte widened to a word, and wi_taps_read stands between the four reads and their decode.  For bytes it pins the words in
+// registers: without it the compiler moves each tap's conversion up under that tap's condition, next to its load, and waits there --
+// four memory latencies per channel in turn where the fp32 instance has its four reads in flight together (measured: 131 us against
+// 75 us for 64 faces of 84 -> 32, profiles/r18_u8_sets.md).  For floats it is nothing
+__device__ __forceinline__ float wi_raw(float v) { return v; }
+__device__ __forceinline__ uint32_t wi_raw(uint8_t b) { return b; }
+__device__ __forceinline__ void wi_taps_read(float&, float&, float&, float&) {}
+__device__ __forceinline__ void wi_taps_read(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
+// four pixels of a little-endian word, in address order
+__device__ __forceinline__ float4 wi_pix4(uint32_t w) {
+    return make_float4(wi_pix((uint8_t)(w & 255u)), wi_pix((uint8_t)((w >> 8) & 255u)), wi_pix((uint8_t)((w >> 16) & 255u)), wi_pix((uint8_t)(w >> 24)));
+}
+// the same copy of a source image of E bytes, decoded into E floats of LDS.  wide 16: a 16-byte aligned set of images of E % 16 == 0
+// bytes, sixteen pixels per lane and load, stored as four 16-byte rows (the widest LDS store: a lane's pixels are 64 contiguous
+// bytes of LDS whatever the store, and the wide one has the fewest lanes per pass on the same banks); wide 4: a 4-byte aligned set
+// of images of E % 4 == 0 bytes, a word per lane and load, lanes side by side in LDS; otherwise bytes.  As above, four loads per
+// lane are issued before the first is used, and a slot past the end of the image moves the lane's first slot once more.  No load
+// reaches past byte E - 1 of the image
+__device__ __forceinline__ void wi_load(const uint8_t* __restrict__ s, float* __restrict__ img, int E, int wide, int tid) {
+    if (wide == 16) {
+        for (int e0 = tid * 16; e0 < E; e0 += 16384) {
+            const int e1 = e0 + 4096 < E ? e0 + 4096 : e0, e2 = e0 + 8192 < E ? e0 + 8192 : e0, e3 = e0 + 12288 < E ? e0 + 12288 : e0;
+            const uint4 v0 = *reinterpret_cast<const uint4*>(s + e0), v1 = *reinterpret_cast<const uint4*>(s + e1);
+            const uint4 v2 = *reinterpret_cast<const uint4*>(s + e2), v3 = *reinterpret_cast<const uint4*>(s + e3);
+            auto put = [&](int e, const uint4& v) {
+                float4* d = reinterpret_cast<float4*>(img + e);
+                d[0] = wi_pix4(v.x); d[1] = wi_pix4(v.y); d[2] = wi_pix4(v.z); d[3] = wi_pix4(v.w);
+            };
+            put(e0, v0);
+            put(e1, v1);
+            put(e2, v2);
+            put(e3, v3);
+        }
+    } else if (wide == 4) {
+        for (int e0 = tid * 4; e0 < E; e0 += 4096) {
+            const int e1 = e0 + 1024 < E ? e0 + 1024 : e0, e2 = e0 + 2048 < E ? e0 + 2048 : e0, e3 = e0 + 3072 < E ? e0 + 3072 : e0;
+            const uint32_t v0 = *reinterpret_cast<const uint32_t*>(s + e0), v1 = *reinterpret_cast<const uint32_t*>(s + e1);
+            const uint32_t v2 = *reinterpret_cast<const uint32_t*>(s + e2), v3 = *reinterpret_cast<const uint32_t*>(s + e3);
+            *reinterpret_cast<float4*>(img + e0) = wi_pix4(v0);
+            *reinterpret_cast<float4*>(img + e1) = wi_pix4(v1);
+            *reinterpret_cast<float4*>(img + e2) = wi_pix4(v2);
+            *reinterpret_cast<float4*>(img + e3) = wi_pix4(v3);
+        }
+    } else {
+        for (int e0 = tid; e0 < E; e0 += 1024) {
+            const int e1 = e0 + 256 < E ? e0 + 256 : e0, e2 = e0 + 512 < E ? e0 + 512 : e0, e3 = e0 + 768 < E ? e0 + 768 : e0;
+            const uint8_t v0 = s[e0], v1 = s[e1], v2 = s[e2], v3 = s[e3];
+            img[e0] = wi_pix(v0);
+            img[e1] = wi_pix(v1);
+            img[e2] = wi_pix(v2);
+            img[e3] = wi_pix(v3);
+        }
+    }
+}
+// the widest load wi_load may use on a byte set: every image base is then aligned to it and no load crosses the end of an image
+static int wi_wide_u8(const uint8_t* set, int E) {
+    return ((size_t)set & 15) == 0 && E % 16 == 0 ? 16 : ((size_t)set & 3) == 0 && E % 4 == 0 ? 4 : 1;
+}
 // fg_warp_images (include/facegen_hip.h): out[j] = clamp01(gains[j] * bilinear(set[idx[j]], affine map mats[j])).
 //   - the source image (c * hs * ws <= 16384 floats) goes to LDS as it lies in the set, 16 bytes per lane where `vec` allows;
 //   - a thread owns output pixels p = tid, tid + 256, ..: the source coordinates, the range test and the four tap offsets are
@@ -159,9 +225,10 @@ __device__ __forceinline__ void wi_load(const float* __restrict__ s, float* __re
 // to LDS before the call (wi_load's copy of the image, the scale plans) is visible to the taps and to everything behind the call.
 // LDS_IMG: `img` is the block's LDS copy, and a tap outside the image reads pixel 0 and drops it; otherwise `img` is the image
 // where it lies in the set (warp_faces_kernel: a photo of any size, taps straight from global memory) and such a tap addresses
-// nothing.  The arithmetic is one
-template <bool SET_NCHW, bool LDS_IMG = true, typename Store>
-__device__ __forceinline__ void wi_warp(const float* __restrict__ img, const float* __restrict__ mats, const float* __restrict__ gains, int j,
+// nothing.  PIX: what `img` holds, floats or, where it is a photo of a byte set, bytes that the tap read decodes (wi_pix).  The
+// arithmetic is one
+template <bool SET_NCHW, bool LDS_IMG = true, typename PIX, typename Store>
+__device__ __forceinline__ void wi_warp(const PIX* __restrict__ img, const float* __restrict__ mats, const float* __restrict__ gains, int j,
                                         int c, int hs, int ws, int ho, int wo, int edge, int tid, Store store) {
 #pragma clang fp contract(off)
     const int Ps = hs * ws;
@@ -202,9 +269,13 @@ __device__ __forceinline__ void wi_warp(const float* __restrict__ img, const flo
         // (a tap outside an LDS image reads the copy of pixel 0 and drops it: four reads in flight per channel, no branch)
         const int ia = (oa < 0 ? 0 : oa) * ts, ib = (ob < 0 ? 0 : ob) * ts, ic = (oc < 0 ? 0 : oc) * ts, id = (od < 0 ? 0 : od) * ts;
         for (int ch = 0; ch < c; ++ch) {
-            const float* pl = img + ch * cs;
-            const float ra = LDS_IMG || oa >= 0 ? pl[ia] : 0.f, rb = LDS_IMG || ob >= 0 ? pl[ib] : 0.f;
-            const float rc = LDS_IMG || oc >= 0 ? pl[ic] : 0.f, rd = LDS_IMG || od >= 0 ? pl[id] : 0.f;
+            const PIX* pl = img + ch * cs;
+            // (the four reads, then the decode of a byte set's taps: wi_taps_read)
+            using RAW = decltype(wi_raw(pl[0]));
+            RAW qa = LDS_IMG || oa >= 0 ? wi_raw(pl[ia]) : RAW(0), qb = LDS_IMG || ob >= 0 ? wi_raw(pl[ib]) : RAW(0);
+            RAW qc = LDS_IMG || oc >= 0 ? wi_raw(pl[ic]) : RAW(0), qd = LDS_IMG || od >= 0 ? wi_raw(pl[id]) : RAW(0);
+            wi_taps_read(qa, qb, qc, qd);
+            const float ra = wi_pix(qa), rb = wi_pix(qb), rc = wi_pix(qc), rd = wi_pix(qd);
             const float a = oa >= 0 ? ra : 0.f, b = ob >= 0 ? rb : 0.f, cc = oc >= 0 ? rc : 0.f, d = od >= 0 ? rd : 0.f;
             const float top = a + (b - a) * fx, bot = cc + (d - cc) * fx;
             float v = top + (bot - top) * fy;
@@ -215,8 +286,8 @@ __device__ __forceinline__ void wi_warp(const float* __restrict__ img, const flo
         if (x >= wo) { x -= wo; ++y; }
     }
 }
-template <bool SET_NCHW, bool OUT_NCHW>
-__global__ __launch_bounds__(256) void warp_images_kernel(const float* __restrict__ set, long long n_set, const int* __restrict__ idx,
+template <bool SET_NCHW, bool OUT_NCHW, typename PIX = float>
+__global__ __launch_bounds__(256) void warp_images_kernel(const PIX* __restrict__ set, long long n_set, const int* __restrict__ idx,
                                                           const float* __restrict__ mats, const float* __restrict__ gains, int c, int hs,
                                                           int ws, int ho, int wo, float* __restrict__ out, int edge, int vec) {
     extern __shared__ float4 wi_lds[];                                      // c * hs * ws floats
@@ -248,6 +319,22 @@ int fg_launch_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c,
                        out, edge, vec)
     FG_BY_LAYOUT(set_nchw, out_nchw, IMAGES)
 #undef IMAGES
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
+// fg_warp_images_u8: the same grid, block and LDS (the block's copy holds decoded floats); `vec` carries wi_wide_u8
+int fg_launch_warp_images_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx,
+                             const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_nchw, int edge) {
+    const int E = c * hs * ws;
+    const size_t lds = ((size_t)E * sizeof(float) + 15) & ~(size_t)15;
+    const int vec = wi_wide_u8(set, E);
+    const dim3 images((unsigned)n);
+    if (c == 1) set_nchw = out_nchw = 1;
+#define IMAGES_U8(SN, ON)                                                                                                        \
+    hipLaunchKernelGGL((warp_images_kernel<SN, ON, uint8_t>), images, dim3(256), lds, ctx->stream, set, n_set, idx, mats, gains, c, hs, ws, \
+                       ho, wo, out, edge, vec)
+    FG_BY_LAYOUT(set_nchw, out_nchw, IMAGES_U8)
+#undef IMAGES_U8
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }
@@ -310,8 +397,8 @@ __device__ __forceinline__ void c2f_up_write(const float* A, const float* B, con
 // fg_warp_c2f (include/facegen_hip.h): fg_warp_images at s x s followed by fg_c2f_coarse_diff, nothing but the requested outputs
 // leaves the block.  A is the source image (wi_load), B takes the warp's stores (stride 1 per channel plane).  The source is dead
 // after the warp: A then takes the cs x cs image.  Up to 135 KB of LDS.
-template <bool SET_NCHW, bool OUT_NCHW>
-__global__ __launch_bounds__(256) void warp_c2f_kernel(const float* __restrict__ set, long long n_set, const int* __restrict__ idx,
+template <bool SET_NCHW, bool OUT_NCHW, typename PIX = float>
+__global__ __launch_bounds__(256) void warp_c2f_kernel(const PIX* __restrict__ set, long long n_set, const int* __restrict__ idx,
                                                        const float* __restrict__ mats, const float* __restrict__ gains, int c, int hs, int ws,
                                                        int s, int cs, float* __restrict__ fine, float* __restrict__ coarse,
                                                        float* __restrict__ diff, int edge, int vec) {
@@ -359,14 +446,36 @@ int fg_launch_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, in
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }
+// fg_warp_c2f_u8: the same grid, block and LDS.  The byte instances are functions of their own: each has its limit raised behind
+// its own key
+int fg_launch_warp_c2f_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx,
+                          const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_nchw,
+                          int edge) {
+    const int E = c * hs * ws, Ec = c * cs * cs;
+    const size_t lds = (((size_t)(((E > Ec ? E : Ec) + 3) & ~3) + (size_t)c * s * s) * sizeof(float) + (size_t)(s + cs) * sizeof(ScaleTerm) + 15) & ~(size_t)15;
+    const int vec = wi_wide_u8(set, E);
+    const dim3 images((unsigned)n);
+    if (c == 1) set_nchw = out_nchw = 1;
+#define C2F_U8(SN, ON)                                                                                                           \
+    static char attr_key;                                                                                                        \
+    if (fg_attr_first(ctx, &attr_key))                                                                                           \
+        FG_HIP(ctx, hipFuncSetAttribute((const void*)warp_c2f_kernel<SN, ON, uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                        (int)(2 * FG_WARP_MAX_FLOATS * sizeof(float) + 2 * 128 * sizeof(ScaleTerm))));           \
+    hipLaunchKernelGGL((warp_c2f_kernel<SN, ON, uint8_t>), images, dim3(256), lds, ctx->stream, set, n_set, idx, mats, gains, c, hs, ws, s, \
+                       cs, fine, coarse, diff, edge, vec)
+    FG_BY_LAYOUT(set_nchw, out_nchw, C2F_U8)
+#undef C2F_U8
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
 // fg_warp_faces (include/facegen_hip.h): the reference's pipeline on a photo of any size.  The photo stays in global memory: wi_warp
 // takes the four taps of every channel of a window pixel straight from it (lanes on neighbouring window pixels read neighbouring
 // addresses of a channel-major photo; a pixel's c floats are adjacent in a pixel-major one) and stores the hw x ww window into A,
 // channel-major.  Stage 2 scales the window to the s x s face in B: scale_bilinear_kernel's body per face element (width pass
 // nested in height pass), through two more runs of plans, T[s + cs .. 2s + cs): ww -> s (columns), T[2s + cs .. 3s + cs): hw -> s
 // (rows); with hw == ww == s the warp writes the face itself.  With cs == 0 the face goes straight to `fine` and nothing follows.
-template <bool SET_NCHW, bool OUT_NCHW>
-__global__ __launch_bounds__(256) void warp_faces_kernel(const float* __restrict__ set, long long n_set, const int* __restrict__ idx,
+template <bool SET_NCHW, bool OUT_NCHW, typename PIX = float>
+__global__ __launch_bounds__(256) void warp_faces_kernel(const PIX* __restrict__ set, long long n_set, const int* __restrict__ idx,
                                                          const float* __restrict__ mats, const float* __restrict__ gains, int c, int hs,
                                                          int ws, int hw, int ww, int s, int cs, float* __restrict__ fine,
                                                          float* __restrict__ coarse, float* __restrict__ diff, int edge) {
@@ -383,7 +492,7 @@ __global__ __launch_bounds__(256) void warp_faces_kernel(const float* __restrict
     if (diff) diff += base;
     const int i = idx[j];
     if (i < 0 || (long long)i >= n_set) { c2f_fill_nan(fine, coarse, diff, Eo, tid); return; }
-    const float* photo = set + (long long)i * ((long long)c * hs * ws);
+    const PIX* photo = set + (long long)i * ((long long)c * hs * ws);
     for (int k = tid; k < 3 * s + cs; k += 256)
         T[k] = k < s ? fg_scale_plan(cs, s, k) : k < s + cs ? fg_scale_plan(s, cs, k - s)
              : k < 2 * s + cs ? fg_scale_plan(ww, s, k - s - cs) : fg_scale_plan(hw, s, k - 2 * s - cs);
@@ -436,6 +545,25 @@ int fg_launch_warp_faces(fg_ctx* ctx, const float* set, long long n_set, int c, 
                        s, cs, fine, coarse, diff, edge)
     FG_BY_LAYOUT(set_nchw, out_nchw, FACES)
 #undef FACES
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
+// fg_warp_faces_u8: the same grid, block and LDS; the taps read single bytes, so any base will do
+int fg_launch_warp_faces_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx,
+                            const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse,
+                            float* diff, int out_nchw, int edge) {
+    const size_t lds = fg_warp_faces_lds_bytes(c, hw, ww, s, cs);
+    const dim3 images((unsigned)n);
+    if (c == 1) set_nchw = out_nchw = 1;
+#define FACES_U8(SN, ON)                                                                                                         \
+    static char attr_key;                                                                                                        \
+    if (fg_attr_first(ctx, &attr_key))                                                                                           \
+        FG_HIP(ctx, hipFuncSetAttribute((const void*)warp_faces_kernel<SN, ON, uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                        (int)FG_FACES_MAX_LDS));                                                                 \
+    hipLaunchKernelGGL((warp_faces_kernel<SN, ON, uint8_t>), images, dim3(256), lds, ctx->stream, set, n_set, idx, mats, gains, c, hs, ws, \
+                       hw, ww, s, cs, fine, coarse, diff, edge)
+    FG_BY_LAYOUT(set_nchw, out_nchw, FACES_U8)
+#undef FACES_U8
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }

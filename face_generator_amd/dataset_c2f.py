@@ -82,6 +82,9 @@ def toResultResident(fineImages, coarseScale, fineScale, ctx=None, augment=None)
     from .runtime import get_context, DeviceDataset, FgError
     ctx = ctx or get_context()
     if isinstance(fineImages, DeviceDataset):
+        if fineImages.storage != "f32":
+            raise FgError("toResultResident: a set stored as bytes is not supported -- the stored coarse and diff fields are computed "
+                          "floats; toResultAugmented computes them per batch from a byte set")
         augment = augment or fineImages.augment
         fineImages = fineImages.images
     if augment is not None:
@@ -171,17 +174,18 @@ class AugmentedResult(_PerPullResult):
                             out_layout=layout, fill=self.augment.fill, ctx=self.ctx)
 
 
-def toResultAugmented(fineImages, coarseScale, fineScale, augment, ctx=None):
+def toResultAugmented(fineImages, coarseScale, fineScale, augment, ctx=None, storage="f32"):
     """toResult for training on freshly augmented faces: fineImages (host or device [N, C, H, W] with H, W >= fineScale, or a
     DeviceDataset without an augmenter) is uploaded once and stays un-augmented in HBM; `augment`, an Augmenter whose out_hw is
-    (fineScale, fineScale), draws the transforms of every pull -> AugmentedResult."""
+    (fineScale, fineScale), draws the transforms of every pull -> AugmentedResult.  storage: DeviceDataset's ("u8": uint8 images
+    stay bytes in HBM, pixels of value b / 255); a DeviceDataset keeps its own."""
     from .runtime import get_context, DeviceDataset, FgError
     ctx = ctx or get_context()
     if not isinstance(fineImages, DeviceDataset):
         fine = torch.as_tensor(fineImages)
         if fine.dim() != 4 or fine.shape[-1] < fineScale or fine.shape[-2] < fineScale:
             raise ValueError("toResultAugmented: fine images must be [N, C, H, W] with H, W >= %d" % fineScale)
-        fineImages = DeviceDataset(ctx, fine)
+        fineImages = DeviceDataset(ctx, fine, storage=storage)
     elif fineImages.augment is not None:
         raise FgError("toResultAugmented: hand the Augmenter over as augment=, not on the DeviceDataset")
     return AugmentedResult(fineImages, coarseScale, fineScale, augment)
@@ -213,11 +217,12 @@ class PhotoResult(_PerPullResult):
         return self.set.gather_fields(indices, self._fields(fields), coarse_scale=self.coarseScale, layout=layout)
 
 
-def toResultPhotos(photos, window_hw, coarseScale, fineScale, augment, ctx=None):
+def toResultPhotos(photos, window_hw, coarseScale, fineScale, augment, ctx=None, storage="f32"):
     """toResult for training on faces cut from whole photos under fresh transforms: photos (host or device [N, C, H, W], any H and
     W, or a runtime.PhotoDataset, which then carries window, fine scale and augmenter itself) is uploaded once and stays in HBM;
     `augment`, an Augmenter whose out_hw is window_hw (or None: the central window, un-augmented), draws the transforms of every
-    pull -> PhotoResult."""
+    pull -> PhotoResult.  storage: PhotoDataset's ("u8": uint8 photos stay bytes in HBM, pixels of value b / 255); a PhotoDataset
+    keeps its own."""
     from .runtime import get_context, PhotoDataset, FgError
     if isinstance(photos, PhotoDataset):
         if augment is not None and augment is not photos.augment:
@@ -225,7 +230,7 @@ def toResultPhotos(photos, window_hw, coarseScale, fineScale, augment, ctx=None)
         if photos.h != int(fineScale) or photos.window_hw != tuple(window_hw if not isinstance(window_hw, int) else (window_hw, window_hw)):
             raise FgError("toResultPhotos: the PhotoDataset hands out %dx%d faces of a %dx%d window" % ((photos.h, photos.w) + photos.window_hw))
         return PhotoResult(photos, coarseScale)
-    return PhotoResult(PhotoDataset(ctx or get_context(), photos, window_hw, int(fineScale), augment=augment), coarseScale)
+    return PhotoResult(PhotoDataset(ctx or get_context(), photos, window_hw, int(fineScale), augment=augment, storage=storage), coarseScale)
 
 
 def toResultDevice(fine_nhwc, coarseScale, ctx=None):

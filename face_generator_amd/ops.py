@@ -184,18 +184,24 @@ def scale_bilinear(x, width, height, layout="nhwc", ctx=None):
     return y
 
 
+def _warp_entry(ctx, name, images):
+    """the entry of a warp for the set's storage: `name` for float32 pixels, its _u8 sibling for a set held as bytes of value b / 255"""
+    return getattr(ctx.lib, name + "_u8" if images.dtype == torch.uint8 else name)
+
+
 def warp_images(images, indices, mats=None, gains=None, out_hw=None, set_layout="nchw", out_layout="nhwc", fill="constant", out=None,
                 ctx=None):
     """out[j] = clamp01(gains[j] * bilinear(images[indices[j]], mats[j])): include/facegen_hip.h fg_warp_images.  images: device
-    [N][C][H][W] (set_layout "nchw") or [N][H][W][C]; indices: device int32 [n]; mats: device float32 [n][6] (output pixel ->
+    [N][C][H][W] (set_layout "nchw") or [N][H][W][C], float32 or uint8 (pixels of value b / 255: fg_warp_images_u8, the same bits as
+    the float set b / 255 gives; warp_c2f and warp_faces likewise); indices: device int32 [n]; mats: device float32 [n][6] (output pixel ->
     source pixel) or None, the identity; gains: device float32 [n] or None (gain 1, no clamp); out_hw: (ho, wo), default the set's;
     fill: "constant" (0 outside the image) or "edge".  -> device [n][ho][wo][C] ("nhwc") or [n][C][ho][wo]."""
     ctx = ctx or get_context()
     layouts, fills = {"nhwc": 0, "nchw": 1}, {"constant": 0, "edge": 1}
     if set_layout not in layouts or out_layout not in layouts or fill not in fills:
         raise ValueError("warp_images: layouts are 'nhwc' / 'nchw', fill is 'constant' / 'edge'")
-    if images.dim() != 4 or images.dtype != torch.float32 or not images.is_contiguous():
-        raise ValueError("warp_images: images must be a contiguous float32 tensor of 4 dimensions")
+    if images.dim() != 4 or images.dtype not in (torch.float32, torch.uint8) or not images.is_contiguous():
+        raise ValueError("warp_images: images must be a contiguous float32 or uint8 tensor of 4 dimensions")
     if layouts[set_layout]:
         N, C, H, W = images.shape
     else:
@@ -216,7 +222,7 @@ def warp_images(images, indices, mats=None, gains=None, out_hw=None, set_layout=
         if t is not None and t.device != ctx.device:
             raise ValueError("warp_images: %s lives on %s, the context on %s" % (name, t.device, ctx.device))
     if n:                                   # (an empty tensor has no address to hand over)
-        ctx.check(ctx.lib.fg_warp_images(ctx.h, images.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
+        ctx.check(_warp_entry(ctx, "fg_warp_images", images)(ctx.h, images.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
                                          None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n,
                                          out.data_ptr(), ho, wo, layouts[out_layout], fills[fill]))
     return out.view(*shape)
@@ -236,8 +242,8 @@ def warp_c2f(images, indices, fine_scale, coarse_scale, mats=None, gains=None, f
     fields = tuple(fields)
     if not fields or len(set(fields)) != len(fields) or any(f not in ("fine", "coarse", "diff") for f in fields):
         raise ValueError("warp_c2f: fields must be a non-empty subset of ('fine', 'coarse', 'diff'), got %r" % (fields,))
-    if images.dim() != 4 or images.dtype != torch.float32 or not images.is_contiguous():
-        raise ValueError("warp_c2f: images must be a contiguous float32 tensor of 4 dimensions")
+    if images.dim() != 4 or images.dtype not in (torch.float32, torch.uint8) or not images.is_contiguous():
+        raise ValueError("warp_c2f: images must be a contiguous float32 or uint8 tensor of 4 dimensions")
     if layouts[set_layout]:
         N, C, H, W = images.shape
     else:
@@ -256,7 +262,7 @@ def warp_c2f(images, indices, fine_scale, coarse_scale, mats=None, gains=None, f
     out = {f: ctx.empty(*shape) for f in fields}
     P = lambda f: out[f].data_ptr() if f in out else None
     if n:                                   # (an empty tensor has no address to hand over)
-        ctx.check(ctx.lib.fg_warp_c2f(ctx.h, images.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
+        ctx.check(_warp_entry(ctx, "fg_warp_c2f", images)(ctx.h, images.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
                                       None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n, s, cs,
                                       P("fine"), P("coarse"), P("diff"), layouts[out_layout], fills[fill]))
     return tuple(out[f] for f in fields)
@@ -278,8 +284,8 @@ def warp_faces(photos, indices, window_hw, s, cs=0, mats=None, gains=None, field
     allowed = ("fine", "coarse", "diff") if cs else ("fine",)
     if not fields or len(set(fields)) != len(fields) or any(f not in allowed for f in fields):
         raise ValueError("warp_faces: fields must be a non-empty subset of %r, got %r" % (allowed, fields))
-    if photos.dim() != 4 or photos.dtype != torch.float32 or not photos.is_contiguous():
-        raise ValueError("warp_faces: photos must be a contiguous float32 tensor of 4 dimensions")
+    if photos.dim() != 4 or photos.dtype not in (torch.float32, torch.uint8) or not photos.is_contiguous():
+        raise ValueError("warp_faces: photos must be a contiguous float32 or uint8 tensor of 4 dimensions")
     if layouts[set_layout]:
         N, C, H, W = photos.shape
     else:
@@ -300,7 +306,7 @@ def warp_faces(photos, indices, window_hw, s, cs=0, mats=None, gains=None, field
     res = {f: ctx.empty(*shape) if out is None else out.view(*shape) for f in fields}
     P = lambda f: res[f].data_ptr() if f in res else None
     if n:                                   # (an empty tensor has no address to hand over)
-        ctx.check(ctx.lib.fg_warp_faces(ctx.h, photos.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
+        ctx.check(_warp_entry(ctx, "fg_warp_faces", photos)(ctx.h, photos.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
                                         None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n, hw, ww,
                                         s, cs, P("fine"), P("coarse"), P("diff"), layouts[out_layout], fills[fill]))
     return tuple(res[f] for f in fields)

@@ -732,6 +732,22 @@ def is_resident(dataset):
     return not torch.is_tensor(dataset) and callable(getattr(dataset, "gather", None))
 
 
+def _resident_pixels(cls, ctx, images, storage, what):
+    """the images of a resident set as they are kept in HBM (cls: the class named in the messages).  storage "f32": float32, any
+    input converted as torch converts it (a uint8 pixel b becomes the float b); "u8": the bytes of a uint8 input, kept as bytes --
+    a pixel b has the value b / 255 and is decoded where the warps read it (include/facegen_hip.h, the _u8 entries)"""
+    if storage not in ("f32", "u8"):
+        raise FgError("%s: storage is 'f32' or 'u8', got %r" % (cls, storage))
+    x = torch.as_tensor(images)
+    if x.dim() != 4 or x.shape[0] < 1:
+        raise FgError("%s: %s must be [N][C][H][W] with N >= 1, got %s" % (cls, what, tuple(x.shape)))
+    if storage == "u8":
+        if x.dtype != torch.uint8:
+            raise FgError("%s: storage='u8' keeps the bytes of a uint8 input, got %s" % (cls, x.dtype))
+        return x.to(ctx.device).contiguous()
+    return x.to(dtype=torch.float32).to(ctx.device).contiguous()
+
+
 def _device_indices(cls, ctx, indices, n_set):
     """the indices() of the resident sets (cls: the class named in the messages)"""
     if isinstance(indices, torch.Tensor) and indices.device.type != "cpu":
@@ -748,17 +764,22 @@ class DeviceDataset:
     """A training set that lives in HBM (train.lua loads N_epoch images once per epoch, adversarial.lua:245 indexes them):
     [N][C][H][W] float32 on the device, the reference's layout and the order NearestSearch streams.  It keeps the reference's
     dataset protocol -- size(), len(), ds[i] -> host CHW tensor (dataset.lua:66-69) -- and adds gather(): dataset[i] for a whole
-    batch of indices as one launch of fg_gather_images, in the layout the steps and the nets take."""
+    batch of indices as one launch of fg_gather_images, in the layout the steps and the nets take.
 
-    def __init__(self, ctx, images, scale=None, augment=None):
-        """images: host or device float32 [N][C][H][W], tensor or array.  scale: side to scale every image to on the device
-        (image.scale, dataset.lua:95) when H, W differ from it.  augment: an Augmenter for gather(), see set_augment()."""
-        self.ctx, self.lib = ctx, ctx.lib
+    storage="u8" keeps a uint8 set as bytes in HBM, a quarter of the float set: a pixel b has the value b / 255, the float the host
+    loaders make of a JPEG's byte, and every pull decodes it in the launch that reads it (fg_warp_images_u8; the un-augmented
+    gather is its identity call, so images above 16384 pixels are refused there).  Every float handed out -- gather, rows, ds[i] --
+    is bit for bit the one the float set b / 255 gives."""
+
+    def __init__(self, ctx, images, scale=None, augment=None, storage="f32"):
+        """images: host or device [N][C][H][W], tensor or array: float32, or uint8 with storage="u8".  scale: side to scale every
+        image to on the device (image.scale, dataset.lua:95) when H, W differ from it; not with storage="u8" (a scaled image is no
+        longer 8-bit).  augment: an Augmenter for gather(), see set_augment()."""
+        self.ctx, self.lib, self.storage = ctx, ctx.lib, storage
         self.set_augment(augment)
-        x = torch.as_tensor(images)
-        if x.dim() != 4 or x.shape[0] < 1:
-            raise FgError("DeviceDataset: images must be [N][C][H][W] with N >= 1, got %s" % (tuple(x.shape),))
-        x = x.to(dtype=torch.float32).to(ctx.device).contiguous()
+        if storage == "u8" and scale is not None:
+            raise FgError("DeviceDataset: storage='u8' takes no scale=, a scaled image is no longer 8-bit")
+        x = _resident_pixels("DeviceDataset", ctx, images, storage, "images")
         if scale is not None and (x.shape[2] != scale or x.shape[3] != scale):
             from . import ops
             x = ops.scale_bilinear(x, int(scale), int(scale), layout="nchw", ctx=ctx)
@@ -775,10 +796,15 @@ class DeviceDataset:
         i = int(i)
         if i < 0 or i >= self.n:
             raise IndexError("DeviceDataset: index %d outside [0, %d)" % (i, self.n))
+        if self.storage == "u8":
+            return self.gather([i], layout="nchw", augment=False)[0].cpu()
         return self.images[i].cpu()
 
     def rows(self, lo, hi):
-        """images lo .. hi-1 as a device view [hi - lo][C][H][W] (no copy)"""
+        """images lo .. hi-1 as device floats [hi - lo][C][H][W]: a view (no copy), or, of a set stored as bytes, decoded by one
+        launch"""
+        if self.storage == "u8":
+            return self.gather(torch.arange(lo, hi, dtype=torch.int32, device=self.ctx.device), layout="nchw", augment=False)
         return self.images[lo:hi]
 
     def indices(self, indices):
@@ -807,7 +833,10 @@ class DeviceDataset:
             out = self.ctx.empty(*shape)
         elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * self.c * self.h * self.w:
             raise FgError("DeviceDataset.gather: out must be a contiguous float32 tensor of %d elements" % (n * self.c * self.h * self.w))
-        if n:                               # (an empty tensor has no address to hand over)
+        if n and self.storage == "u8":      # the identity call: fg_gather_images' bits, decoded (no matrices, no gains)
+            self.ctx.check(self.lib.fg_warp_images_u8(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1, idx.data_ptr(),
+                                                      None, None, n, out.data_ptr(), self.h, self.w, 0 if layout == "nhwc" else 1, 0))
+        elif n:                             # (an empty tensor has no address to hand over)
             self.ctx.check(self.lib.fg_gather_images(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1,
                                                      idx.data_ptr(), n, out.data_ptr(), 0 if layout == "nhwc" else 1))
         return out.view(*shape)
@@ -824,9 +853,9 @@ class DeviceDataset:
             raise FgError("DeviceDataset.gather: out must be a contiguous float32 tensor of %d elements" % (n * self.c * ho * wo))
         if n:
             both = aug.draw_device(self.ctx, n, (self.h, self.w))
-            self.ctx.check(self.lib.fg_warp_images(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1, idx.data_ptr(),
-                                                   both.data_ptr(), both.data_ptr() + 24 * n, n, out.data_ptr(), ho, wo,
-                                                   0 if layout == "nhwc" else 1, aug.fill_code))
+            warp = self.lib.fg_warp_images_u8 if self.storage == "u8" else self.lib.fg_warp_images
+            self.ctx.check(warp(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1, idx.data_ptr(), both.data_ptr(),
+                                both.data_ptr() + 24 * n, n, out.data_ptr(), ho, wo, 0 if layout == "nhwc" else 1, aug.fill_code))
         return out.view(*shape)
 
 
@@ -1000,12 +1029,10 @@ class PhotoDataset:
     The dataset protocol is DeviceDataset's: size(), len(), ds[i] -> the host CHW face of the central window under the identity,
     indices(), rows(), gather(); is_resident() is true for it."""
 
-    def __init__(self, ctx, photos, window_hw, out_hw, augment=None):
-        self.ctx, self.lib = ctx, ctx.lib
-        x = torch.as_tensor(photos)
-        if x.dim() != 4 or x.shape[0] < 1:
-            raise FgError("PhotoDataset: photos must be [N][C][H][W] with N >= 1, got %s" % (tuple(x.shape),))
-        self.photos = x.to(dtype=torch.float32).to(ctx.device).contiguous()
+    def __init__(self, ctx, photos, window_hw, out_hw, augment=None, storage="f32"):
+        """storage="u8": uint8 photos stay bytes in HBM, a pixel b has the value b / 255 (fg_warp_faces_u8), as DeviceDataset's"""
+        self.ctx, self.lib, self.storage = ctx, ctx.lib, storage
+        self.photos = _resident_pixels("PhotoDataset", ctx, photos, storage, "photos")
         self.n, self.c, self.photo_h, self.photo_w = (int(v) for v in self.photos.shape)
         self.window_hw = (int(window_hw), int(window_hw)) if isinstance(window_hw, int) else (int(window_hw[0]), int(window_hw[1]))
         sides = (out_hw, out_hw) if isinstance(out_hw, int) else tuple(out_hw)

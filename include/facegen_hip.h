@@ -643,6 +643,37 @@ int fg_warp_faces(fg_ctx* ctx, const float* set, long long n_set, int c, int hs,
                   const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff,
                   int out_layout, int fill);
 
+/* ---- the three warps on a set held as 8-bit pixels: every pixel the reference loads is one byte of a JPEG divided by 255
+ *      (image.load(.., "float"), dataset.lua:90 and :200), so a resident set kept as bytes takes a quarter of the HBM and loses
+ *      nothing.  The bytes stay bytes in HBM and are decoded where they are read. ----
+ * set: n_set images of c * hs * ws device bytes in set_layout.  The value of a byte b is
+ *     p(b) = (float)b / 255.0f,
+ *   the correctly rounded fp32 quotient (a true division: b * (1 / 255) is another float for 126 of the 256 bytes) -- what
+ *   np.float32(b) / np.float32(255) gives, the float the host loaders produce.
+ * Bits: every float an _u8 entry writes equals, bit for bit, what its fp32 sibling (the entry of the same name without the suffix)
+ *   writes for the float set p(set) and the same other arguments: every layout pair, both fills, mats and gains NULL or given,
+ *   every subset of fine / coarse / diff.  With mats == NULL and gains == NULL the entries decode: out[j] = p(set[idx[j]]).
+ * Everything else is the sibling's contract: the meaning of every other argument, the refusals and their codes (a message names
+ *   the _u8 entry), an idx[j] outside [0, n_set) reads nothing and gives a quiet-NaN image (0x7fc00000) in every requested output,
+ *   the 64-bit base offset of an image, n == 0, nothing written outside the requested outputs, one launch on the context's stream
+ *   with the sibling's grid, block and LDS size, no scratch, no atomics, no synchronisation.
+ * Limits, unchanged and counted in pixels: c * hs * ws <= 16384 for fg_warp_images_u8 and fg_warp_c2f_u8 (the block's copy of the
+ *   source image in LDS holds decoded floats), c * s * s <= 16384 for fg_warp_c2f_u8; fg_warp_faces_u8 takes photos of any size
+ *   below 2^31 pixels under the LDS formula of fg_warp_faces.
+ * Alignment: one byte is enough, for any base and any image size.  Nothing outside set[0 .. n_set * c * hs * ws) is read.  The copy
+ *   of the source image (fg_warp_images_u8, fg_warp_c2f_u8) uses 16-byte loads only when `set` is 16-byte aligned and c * hs * ws
+ *   % 16 == 0, 4-byte loads only when `set` is 4-byte aligned and c * hs * ws % 4 == 0, byte loads otherwise: no load reaches over
+ *   the end of an image.  fg_warp_faces_u8 reads single bytes.  There is no fg_gather_images for bytes: the un-augmented pull of a
+ *   byte set is the identity call (mats == NULL, gains == NULL) of fg_warp_images_u8 or fg_warp_faces_u8. */
+int fg_warp_images_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx,
+                      const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill);
+int fg_warp_c2f_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx,
+                   const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout,
+                   int fill);
+int fg_warp_faces_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx,
+                     const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff,
+                     int out_layout, int fill);
+
 /* ---- the random transforms of dataset/generate_dataset.py (:43-48 and its create_aug_matrices: flip, zoom, rotation, shear,
  *      translation, brightness) drawn, assembled into matrices and left on the device: the mats / gains of fg_warp_images and
  *      fg_warp_c2f for n images in one launch, no host arithmetic and no upload per batch. ----

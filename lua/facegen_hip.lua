@@ -151,6 +151,9 @@ int fg_gather_images(fg_ctx* ctx, const float* set, long long n_set, int c, int 
 int fg_warp_images(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill);
 int fg_warp_c2f(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill);
 int fg_warp_faces(fg_ctx* ctx, const float* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill);
+int fg_warp_images_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill);
+int fg_warp_c2f_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill);
+int fg_warp_faces_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill);
 typedef struct fg_augment_spec { int hflip, vflip; int zoom_equal; double zoom_lo, zoom_hi; int rot_lo, rot_hi; int shear_lo, shear_hi; int tx_lo, tx_hi, ty_lo, ty_hi; double gain_lo, gain_hi; } fg_augment_spec;
 int fg_draw_transforms(fg_ctx* ctx, const fg_augment_spec* spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo, float* mats, float* gains);
 int fg_scale_bilinear(fg_ctx* ctx, const float* src, float* dst, int n, int c, int hs, int ws, int hd, int wd, int layout);
@@ -811,17 +814,36 @@ function M.gatherImages(set, nSet, c, h, w, setLayout, idx, n, out, outLayout)
     check(C.fg_gather_images(ctx, set.ptr, nSet, c, h, w, setLayout, ffi.cast('const int*', idx.ptr), n, out.ptr, outLayout))
     return out
 end
--- FG.Dataset(images): a host FloatTensor [N][C][H][W] uploaded once.  It keeps dataset.lua's protocol -- ds:size(), ds[i] -> host CHW
+-- FG.Dataset(images): a host FloatTensor [N][C][H][W], or FG.u8(a ByteTensor) of that shape (below), uploaded once.  It keeps dataset.lua's protocol -- ds:size(), ds[i] -> host CHW
 -- FloatTensor (1-based, one small copy) -- and adds ds:gather(picks): the batch {ds[picks[1]], ...} as a device NHWC tensor, one launch
 local Dataset = {}
 Dataset.__index = function(self, k)
     if type(k) == 'number' then return Dataset.get(self, k) end
     return Dataset[k]
 end
+-- FG.u8(bytes): the option storage = 'u8' of FG.Dataset, FG.augmentedResult, FG.photoDataset and FG.photoResult -- hand FG.u8(t) over in
+-- place of the images and the ByteTensor t stays bytes in HBM, a quarter of the float set.  A pixel b has the value b / 255 and is
+-- decoded in the launch that reads it (the fg_warp_*_u8 entries): every float handed out is bit for bit the one the float set b / 255
+-- gives.  Without the tag every input is stored as floats, a ByteTensor included (images:float(), the byte's own value)
+local U8 = {}
+function M.u8(bytes)
+    assert(torch.isTensor(bytes) and bytes:type() == 'torch.ByteTensor', 'FG.u8: a ByteTensor')
+    return setmetatable({tensor = bytes}, U8)
+end
+-- images or FG.u8(images) -> the host tensor, its copy in HBM (DeviceTensor; of bytes: padded to whole words, .bytes its typed pointer)
+-- and the storage, 'f32' or 'u8'
+local function residentPixels(images)
+    if getmetatable(images) ~= U8 then return images, M.DeviceTensor(images:nElement()):copy(images:float()), 'f32' end
+    local host = images.tensor:contiguous()
+    local dev = M.DeviceTensor(math.ceil(host:nElement() / 4))
+    check(C.fg_h2d(ctx, dev.ptr, host:data(), host:nElement()))
+    dev.bytes = ffi.cast('const uint8_t*', dev.ptr)
+    return host, dev, 'u8'
+end
 function M.Dataset(images)
-    assert(images:dim() == 4 and images:size(1) >= 1, 'FG.Dataset: [N][C][H][W] with N >= 1')
-    return setmetatable({images = M.DeviceTensor(images:nElement()):copy(images:float()), n = images:size(1), c = images:size(2),
-                         h = images:size(3), w = images:size(4)}, Dataset)
+    local host, dev, storage = residentPixels(images)
+    assert(host:dim() == 4 and host:size(1) >= 1, 'FG.Dataset: [N][C][H][W] with N >= 1')
+    return setmetatable({images = dev, n = host:size(1), c = host:size(2), h = host:size(3), w = host:size(4), storage = storage}, Dataset)
 end
 function M.isDataset(x) return type(x) == 'table' and getmetatable(x) == Dataset end
 function Dataset:size() return self.n end
@@ -829,7 +851,12 @@ function Dataset:get(i)
     assert(i >= 1 and i <= self.n, 'FG.Dataset: index out of range')
     local e = self.c * self.h * self.w
     local t = torch.FloatTensor(self.c, self.h, self.w)
-    check(C.fg_d2h(ctx, t:data(), self.images.ptr + (i - 1) * e, e * 4))
+    if self.storage == 'u8' then                -- decoded by the identity launch, CHW
+        local image = self:gather({i}, 1, 1)
+        check(C.fg_d2h(ctx, t:data(), image.ptr, e * 4))
+    else
+        check(C.fg_d2h(ctx, t:data(), self.images.ptr + (i - 1) * e, e * 4))
+    end
     return t
 end
 -- picks: a Lua table of 1-based indices (range-checked here, one upload), or a DeviceTensor of 0-based int32 with its count n
@@ -845,6 +872,7 @@ function Dataset:gather(picks, n, outLayout)
         idx = M.indexTensor(zero)
     end
     local out = M.DeviceTensor(n * self.c * self.h * self.w)
+    if self.storage == 'u8' then return self:gatherWarped(idx, n, nil, nil, out, outLayout or 0, 0), idx end     -- the identity call
     return M.gatherImages(self.images, self.n, self.c, self.h, self.w, 1, idx, n, out, outLayout or 0), idx
 end
 -- fg_warp_images: out[j] = clamp01(gains[j] * bilinear(set[idx[j]], mats[j])), the augmentation of dataset/generate_dataset.py per batch.
@@ -859,6 +887,11 @@ end
 -- set's own size (a crop of a set with a margin: M.warpImages); idx: a DeviceTensor of 0-based int32 (M.indexTensor) with its count n
 function Dataset:gatherWarped(idx, n, mats, gains, out, outLayout, fill)
     out = out or M.DeviceTensor(n * self.c * self.h * self.w)
+    if self.storage == 'u8' then
+        check(C.fg_warp_images_u8(ctx, self.images.bytes, self.n, self.c, self.h, self.w, 1, ffi.cast('const int*', idx.ptr),
+                                  mats and mats.ptr or nil, gains and gains.ptr or nil, n, out.ptr, self.h, self.w, outLayout or 0, fill or 0))
+        return out
+    end
     return M.warpImages(self.images, self.n, self.c, self.h, self.w, 1, idx, mats, gains, n, out, self.h, self.w, outLayout or 0, fill or 0)
 end
 -- dataset._toResult (dataset_c2f.lua:49-63) with the three sets left in HBM: {fine, coarse, diff} as FG.Datasets, :size(), [i]
@@ -876,6 +909,12 @@ end
 -- scale(scale(fine, cs, cs), s, s), diff = fine - coarse.  fine / coarse / diff: DeviceTensors of n * c * s * s floats in outLayout, or
 -- nil: not wanted, not written (at least one is given); idx, mats, gains, fill as ds:gatherWarped.  Returns fine, coarse, diff
 function Dataset:gatherWarpedC2F(idx, n, mats, gains, s, cs, fine, coarse, diff, outLayout, fill)
+    if self.storage == 'u8' then
+        check(C.fg_warp_c2f_u8(ctx, self.images.bytes, self.n, self.c, self.h, self.w, 1, ffi.cast('const int*', idx.ptr),
+                               mats and mats.ptr or nil, gains and gains.ptr or nil, n, s, cs, fine and fine.ptr or nil,
+                               coarse and coarse.ptr or nil, diff and diff.ptr or nil, outLayout or 0, fill or 0))
+        return fine, coarse, diff
+    end
     check(C.fg_warp_c2f(ctx, self.images.ptr, self.n, self.c, self.h, self.w, 1, ffi.cast('const int*', idx.ptr), mats and mats.ptr or nil,
                         gains and gains.ptr or nil, n, s, cs, fine and fine.ptr or nil, coarse and coarse.ptr or nil, diff and diff.ptr or nil,
                         outLayout or 0, fill or 0))
@@ -931,12 +970,14 @@ Photos.__index = function(self, k)
     return Photos[k]
 end
 function M.photoDataset(photos, windowH, windowW, s, draw, fill)
+    local host, dev, storage = residentPixels(photos)      -- (FG.u8(photos): the photos stay bytes in HBM, as FG.Dataset's)
+    photos = host
     assert(photos:dim() == 4 and photos:size(1) >= 1, 'FG.photoDataset: [N][C][H][W] with N >= 1')
     assert(windowH >= 1 and windowW >= 1 and s >= 1, 'FG.photoDataset: positive sizes')
     assert(draw == nil or type(draw) == 'function', 'FG.photoDataset: draw(n, hs, ws) -> mats, gains')
-    return setmetatable({photos = M.DeviceTensor(photos:nElement()):copy(photos:float()), n = photos:size(1), c = photos:size(2),
+    return setmetatable({photos = dev, n = photos:size(1), c = photos:size(2),
                          photoH = photos:size(3), photoW = photos:size(4), windowH = windowH, windowW = windowW, h = s, w = s, draw = draw,
-                         fill = fill or 0}, Photos)
+                         fill = fill or 0, storage = storage}, Photos)
 end
 function M.isPhotoDataset(x) return type(x) == 'table' and getmetatable(x) == Photos end
 function Photos:size() return self.n end
@@ -967,9 +1008,15 @@ function Photos:gatherFields(picks, fields, cs, n, outLayout, augment)
     end
     local mats, gains
     if self.draw and augment ~= false then mats, gains = self.draw(n, self.photoH, self.photoW) else mats = self:identity(n) end
-    check(C.fg_warp_faces(ctx, self.photos.ptr, self.n, self.c, self.photoH, self.photoW, 1, ffi.cast('const int*', idx.ptr), mats.ptr,
-                          gains and gains.ptr or nil, n, self.windowH, self.windowW, s, cs, out.fine and out.fine.ptr or nil,
-                          out.coarse and out.coarse.ptr or nil, out.diff and out.diff.ptr or nil, outLayout or 0, self.fill))
+    if self.storage == 'u8' then
+        check(C.fg_warp_faces_u8(ctx, self.photos.bytes, self.n, self.c, self.photoH, self.photoW, 1, ffi.cast('const int*', idx.ptr), mats.ptr,
+                                 gains and gains.ptr or nil, n, self.windowH, self.windowW, s, cs, out.fine and out.fine.ptr or nil,
+                                 out.coarse and out.coarse.ptr or nil, out.diff and out.diff.ptr or nil, outLayout or 0, self.fill))
+    else
+        check(C.fg_warp_faces(ctx, self.photos.ptr, self.n, self.c, self.photoH, self.photoW, 1, ffi.cast('const int*', idx.ptr), mats.ptr,
+                              gains and gains.ptr or nil, n, self.windowH, self.windowW, s, cs, out.fine and out.fine.ptr or nil,
+                              out.coarse and out.coarse.ptr or nil, out.diff and out.diff.ptr or nil, outLayout or 0, self.fill))
+    end
     local res = {}
     for i, f in ipairs(fields) do res[i] = out[f] end
     return unpack(res)
