@@ -376,6 +376,33 @@ int fg_warp_faces_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, in
     if (r != FG_OK || n == 0) return r;
     return fg_launch_warp_faces_u8(ctx, set, n_set, c, hs, ws, set_layout, idx, mats, gains, n, hw, ww, s, cs, fine, coarse, diff, out_layout, fill);
 }
+// The _u8_y entries: R, G, B bytes in, one channel of luma out.  The checks are the siblings' at c == 1 (one channel: the batch's
+// two layouts are one order, so out_layout is handed over as 1), the limits count luma floats
+int fg_warp_images_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                        const float* gains, int n, float* out, int ho, int wo, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    const int r = warp_images_check(ctx, "fg_warp_images_u8_y", set, n_set, 1, hs, ws, set_layout, idx, mats, n, out, ho, wo, 1, fill);
+    if (r != FG_OK || n == 0) return r;
+    return fg_launch_warp_images_u8_y(ctx, set, n_set, hs, ws, set_layout, idx, mats, gains, n, out, ho, wo, fill);
+}
+int fg_warp_c2f_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                     const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    const int r = warp_c2f_check(ctx, "fg_warp_c2f_u8_y", set, n_set, 1, hs, ws, set_layout, idx, mats, n, s, cs, fine, coarse, diff, 1, fill);
+    if (r != FG_OK || n == 0) return r;
+    return fg_launch_warp_c2f_u8_y(ctx, set, n_set, hs, ws, set_layout, idx, mats, gains, n, s, cs, fine, coarse, diff, fill);
+}
+int fg_warp_faces_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_layout, const int* idx, const float* mats,
+                       const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int fill) {
+    NEED(ctx, ctx, "null ctx");
+    const int r = warp_faces_check(ctx, "fg_warp_faces_u8_y", set, n_set, 1, hs, ws, set_layout, idx, mats, n, hw, ww, s, cs, fine, coarse, diff, 1, fill);
+    if (r != FG_OK) return r;
+    // (a photo is three bytes per pixel: offsets inside it are 32-bit)
+    if (3LL * hs >= (1LL << 31) || 3LL * hs * ws >= (1LL << 31))
+        return fg_set_err(ctx, FG_ERR_INVALID, "fg_warp_faces_u8_y: a photo of 3 x %d x %d bytes is 2^31 bytes or more", hs, ws);
+    if (n == 0) return r;
+    return fg_launch_warp_faces_u8_y(ctx, set, n_set, hs, ws, set_layout, idx, mats, gains, n, hw, ww, s, cs, fine, coarse, diff, fill);
+}
 // what is wrong with a spec, or NULL: every range lo <= hi, the integer ones at most 2^31 values wide (the pick is a 32 x 32 bit product)
 static const char* augment_spec_fault(const fg_augment_spec& s) {
     auto wide = [](int lo, int hi) { return (long long)hi - lo + 1 > (1LL << 31); };

@@ -621,6 +621,15 @@ int fg_launch_warp_c2f_u8(fg_ctx*, const uint8_t* set, long long n_set, int c, i
 int fg_launch_warp_faces_u8(fg_ctx*, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_nchw, const int* idx,
                             const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse,
                             float* diff, int out_nchw, int edge);
+// the _u8_y entries: the three warps on a set of R, G, B bytes (3 * hs * ws per image, pixel-major or three planes) read as luma,
+// Y = ((0.299f * p(r)) + (0.587f * p(g))) + (0.114f * p(b)) formed where global memory is read; one channel out, so no c and no
+// out_nchw.  Grids, blocks, LDS sizes and limits are the fp32 launchers' at c == 1; any alignment of `set`
+int fg_launch_warp_images_u8_y(fg_ctx*, const uint8_t* set, long long n_set, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                               const float* gains, int n, float* out, int ho, int wo, int edge);
+int fg_launch_warp_c2f_u8_y(fg_ctx*, const uint8_t* set, long long n_set, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                            const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int edge);
+int fg_launch_warp_faces_u8_y(fg_ctx*, const uint8_t* set, long long n_set, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                              const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int edge);
 // fg_draw_transforms: image j takes the quads offset + 3j .. offset + 3j + 2 of the Philox stream; the spec is checked by the entry
 int fg_launch_draw_transforms(fg_ctx*, const fg_augment_spec& spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo,
                               float* mats, float* gains);

@@ -1,6 +1,6 @@
 // The device data path for gfx950 (wave = 64): image.scale, the warps of an HBM-resident image set (fg_warp_images, fg_warp_c2f,
-// fg_warp_faces; their _u8 siblings on a set of 8-bit pixels are instances of the same kernels) and the draw of their transforms
-// (fg_draw_transforms).  One kernel name per entry.  The gather (fg_gather_images)
+// fg_warp_faces; their _u8 siblings on a set of 8-bit pixels and the _u8_y ones, luma of R, G, B bytes, are instances of the same
+// kernels) and the draw of their transforms (fg_draw_transforms).  One kernel name per entry.  The gather (fg_gather_images)
 // is in pointwise.hip: it shares its tile code with the layout kernels of the step path.
 // Reference semantics: include/facegen_hip.h (dataset_c2f.lua:53-61, dataset.lua:95, generate_dataset.py).
 #include "fg_internal.h"
@@ -156,6 +156,18 @@ __device__ __forceinline__ float wi_raw(float v) { return v; }
 __device__ __forceinline__ uint32_t wi_raw(uint8_t b) { return b; }
 __device__ __forceinline__ void wi_taps_read(float&, float&, float&, float&) {}
 __device__ __forceinline__ void wi_taps_read(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
+// (a luma set: the twelve words of four taps from planes, or of the four slots of wi_load_luma, W = uint32_t or four words; the
+// eight words of four taps from triples.  One statement each, over the words as they are loaded: nothing is taken out of a word,
+// and so nothing waits for one, before all are read)
+typedef uint32_t wi_u32x4 __attribute__((ext_vector_type(4)));
+template <typename W>
+__device__ __forceinline__ void wi_taps_read(W& a0, W& a1, W& a2, W& b0, W& b1, W& b2, W& c0, W& c1, W& c2, W& d0, W& d1, W& d2) {
+    asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(c0), "+v"(c1), "+v"(c2), "+v"(d0), "+v"(d1), "+v"(d2));
+}
+__device__ __forceinline__ void wi_taps_read(uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1, uint32_t& c0, uint32_t& c1, uint32_t& d0,
+                                             uint32_t& d1) {
+    asm volatile("" : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1), "+v"(c0), "+v"(c1), "+v"(d0), "+v"(d1));
+}
 // four pixels of a little-endian word, in address order
 __device__ __forceinline__ float4 wi_pix4(uint32_t w) {
     return make_float4(wi_pix((uint8_t)(w & 255u)), wi_pix((uint8_t)((w >> 8) & 255u)), wi_pix((uint8_t)((w >> 16) & 255u)), wi_pix((uint8_t)(w >> 24)));
@@ -205,6 +217,81 @@ __device__ __forceinline__ void wi_load(const uint8_t* __restrict__ s, float* __
 // the widest load wi_load may use on a byte set: every image base is then aligned to it and no load crosses the end of an image
 static int wi_wide_u8(const uint8_t* set, int E) {
     return ((size_t)set & 15) == 0 && E % 16 == 0 ? 16 : ((size_t)set & 3) == 0 && E % 4 == 0 ? 4 : 1;
+}
+// A set of R, G, B bytes read as luma (the _u8_y entries, PIX = wi_y8, a tag: a set of wi_y8 is three bytes per pixel and the kernels
+// run at c == 1).  The value of a pixel is Torch7's image.rgb2y on the floats p(b) = b / 255,
+//     Y = ((0.299f * p(r)) + (0.587f * p(g))) + (0.114f * p(b)),
+// every product and sum rounded on its own in this order (no FMA contraction; the constants are the floats nearest to the decimals).
+// As with the bytes it is formed where the pixel leaves global memory, so everything behind it is the fp32 code at c == 1
+struct wi_y8 { uint8_t b; };
+template <typename PIX> struct wi_is_luma { static constexpr bool value = false; };
+template <> struct wi_is_luma<wi_y8> { static constexpr bool value = true; };
+__device__ __forceinline__ float wi_luma(uint32_t r, uint32_t g, uint32_t b) {
+#pragma clang fp contract(off)
+    const float yr = 0x1.322d0ep-2f * wi_pix(r), yg = 0x1.2c8b44p-1f * wi_pix(g), yb = 0x1.d2f1aap-4f * wi_pix(b);
+    return (yr + yg) + yb;
+}
+// byte k (address order) of the little-endian words w[]
+__device__ __forceinline__ uint32_t wi_byte(const uint32_t* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
+// the words of a load as it sits in registers, R = wi_u32x4 (16 bytes in address order) / uint32_t (a word, or a byte widened)
+__device__ __forceinline__ void wi_words(const wi_u32x4& v, uint32_t* w) { w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+__device__ __forceinline__ void wi_words(const uint32_t& v, uint32_t* w) { w[0] = v; }
+// wi_load for a luma set: the image at `s` is 3 P bytes (PLANES: the planes R, G, B of P bytes each; otherwise P triples R, G, B),
+// LDS takes its P luma floats.  A slot is W = sizeof(V) pixels of a lane: three loads of W bytes, one from each plane at the same
+// offset, or the 3 W contiguous bytes of the W triples.  wide 16 / 4 (V = wi_u32x4 / uint32_t): `set` is aligned to W and
+// P % W == 0, so the image's base 3 P i, the plane offsets P and 2 P and the slots 3 W k are aligned to W and no slot straddles the
+// end of a plane or of the image; otherwise single bytes.  wi_load's shape: the loads of four slots per lane (twelve) are issued
+// before the first is used, and a slot past the end moves the lane's first slot once more.  The twelve loaded registers (48 words
+// at the 16-byte width) are pinned between the loads and the decode (wi_taps_read): left alone, the compiler decodes the 16-byte
+// slots one at a time, each behind a wait of its own.  No load reaches past byte 3 P - 1 of the image
+template <bool PLANES, typename V>
+__device__ __forceinline__ void wi_load_luma_as(const uint8_t* __restrict__ s, float* __restrict__ img, int P, int tid) {
+    constexpr int W = (int)sizeof(V), NW = W < 4 ? 1 : W / 4;
+    using R = decltype(V() + 0u);                                           // uint8_t widens to a word
+    struct Slot { R a, b, c; };
+    auto get = [&](int e) {
+        const uint8_t* q = PLANES ? s + e : s + 3 * e;
+        const int step = PLANES ? P : W;
+        Slot t;
+        t.a = *reinterpret_cast<const V*>(q); t.b = *reinterpret_cast<const V*>(q + step); t.c = *reinterpret_cast<const V*>(q + 2 * step);
+        return t;
+    };
+    auto put = [&](int e, const Slot& t) {
+        uint32_t w[3 * NW];
+        wi_words(t.a, w); wi_words(t.b, w + NW); wi_words(t.c, w + 2 * NW);
+        float y[W];
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            if (W == 1) y[k] = wi_luma(w[0], w[1], w[2]);
+            else if (PLANES) y[k] = wi_luma(wi_byte(w, k), wi_byte(w + NW, k), wi_byte(w + 2 * NW, k));
+            else y[k] = wi_luma(wi_byte(w, 3 * k), wi_byte(w, 3 * k + 1), wi_byte(w, 3 * k + 2));
+        }
+        if (W == 1) img[e] = y[0];
+        else {
+#pragma unroll
+            for (int k = 0; k < W; k += 4) *reinterpret_cast<float4*>(img + e + k) = make_float4(y[k], y[k + 1], y[k + 2], y[k + 3]);
+        }
+    };
+    for (int e0 = tid * W; e0 < P; e0 += 1024 * W) {
+        const int e1 = e0 + 256 * W < P ? e0 + 256 * W : e0, e2 = e0 + 512 * W < P ? e0 + 512 * W : e0, e3 = e0 + 768 * W < P ? e0 + 768 * W : e0;
+        Slot t0 = get(e0), t1 = get(e1), t2 = get(e2), t3 = get(e3);
+        wi_taps_read(t0.a, t0.b, t0.c, t1.a, t1.b, t1.c, t2.a, t2.b, t2.c, t3.a, t3.b, t3.c);
+        put(e0, t0);
+        put(e1, t1);
+        put(e2, t2);
+        put(e3, t3);
+    }
+}
+template <bool PLANES>
+__device__ __forceinline__ void wi_load_luma(const uint8_t* __restrict__ s, float* __restrict__ img, int P, int wide, int tid) {
+    if (wide == 16) wi_load_luma_as<PLANES, wi_u32x4>(s, img, P, tid);
+    else if (wide == 4) wi_load_luma_as<PLANES, uint32_t>(s, img, P, tid);
+    else wi_load_luma_as<PLANES, uint8_t>(s, img, P, tid);
+}
+// the widest load wi_load_luma may use, in either layout: with `set` aligned to it and P % width == 0 every image base, plane and
+// slot is aligned to it and no load crosses the end of a plane or of an image (3 P % 16 == 0 is P % 16 == 0)
+static int wi_wide_u8_y(const uint8_t* set, int P) {
+    return ((size_t)set & 15) == 0 && P % 16 == 0 ? 16 : ((size_t)set & 3) == 0 && P % 4 == 0 ? 4 : 1;
 }
 // fg_warp_images (include/facegen_hip.h): out[j] = clamp01(gains[j] * bilinear(set[idx[j]], affine map mats[j])).
 //   - the source image (c * hs * ws <= 16384 floats) goes to LDS as it lies in the set, 16 bytes per lane where `vec` allows;
@@ -269,13 +356,40 @@ __device__ __forceinline__ void wi_warp(const PIX* __restrict__ img, const float
         // (a tap outside an LDS image reads the copy of pixel 0 and drops it: four reads in flight per channel, no branch)
         const int ia = (oa < 0 ? 0 : oa) * ts, ib = (ob < 0 ? 0 : ob) * ts, ic = (oc < 0 ? 0 : oc) * ts, id = (od < 0 ? 0 : od) * ts;
         for (int ch = 0; ch < c; ++ch) {
-            const PIX* pl = img + ch * cs;
-            // (the four reads, then the decode of a byte set's taps: wi_taps_read)
-            using RAW = decltype(wi_raw(pl[0]));
-            RAW qa = LDS_IMG || oa >= 0 ? wi_raw(pl[ia]) : RAW(0), qb = LDS_IMG || ob >= 0 ? wi_raw(pl[ib]) : RAW(0);
-            RAW qc = LDS_IMG || oc >= 0 ? wi_raw(pl[ic]) : RAW(0), qd = LDS_IMG || od >= 0 ? wi_raw(pl[id]) : RAW(0);
-            wi_taps_read(qa, qb, qc, qd);
-            const float ra = wi_pix(qa), rb = wi_pix(qb), rc = wi_pix(qc), rd = wi_pix(qd);
+            float ra, rb, rc, rd;
+            if constexpr (wi_is_luma<PIX>::value) {
+                // a photo of a luma set (c == 1, never an LDS image): the R, G, B bytes of the four taps, all read in front of the
+                // first decode (wi_taps_read).  Planes: byte o of each plane, twelve reads.  Triples: the triple at 3 o as its
+                // first two bytes in one 2-byte read (at any address) and its third, eight reads -- what the compiler makes of
+                // three byte reads too, but then it takes R and G apart next to their read and waits there, tap after tap
+                const uint8_t* ph = &img->b;
+                if constexpr (SET_NCHW) {
+                    uint32_t a0 = oa >= 0 ? ph[oa] : 0u, a1 = oa >= 0 ? ph[oa + Ps] : 0u, a2 = oa >= 0 ? ph[oa + 2 * Ps] : 0u;
+                    uint32_t b0 = ob >= 0 ? ph[ob] : 0u, b1 = ob >= 0 ? ph[ob + Ps] : 0u, b2 = ob >= 0 ? ph[ob + 2 * Ps] : 0u;
+                    uint32_t c0 = oc >= 0 ? ph[oc] : 0u, c1 = oc >= 0 ? ph[oc + Ps] : 0u, c2 = oc >= 0 ? ph[oc + 2 * Ps] : 0u;
+                    uint32_t d0 = od >= 0 ? ph[od] : 0u, d1 = od >= 0 ? ph[od + Ps] : 0u, d2 = od >= 0 ? ph[od + 2 * Ps] : 0u;
+                    wi_taps_read(a0, a1, a2, b0, b1, b2, c0, c1, c2, d0, d1, d2);
+                    ra = wi_luma(a0, a1, a2); rb = wi_luma(b0, b1, b2); rc = wi_luma(c0, c1, c2); rd = wi_luma(d0, d1, d2);
+                } else {
+                    typedef uint16_t __attribute__((aligned(1))) rg_t;          // R, G of a triple, little-endian: G in the high byte
+                    auto rg = [&](int o) -> uint32_t { return *reinterpret_cast<const rg_t*>(ph + 3 * o); };
+                    uint32_t a0 = oa >= 0 ? rg(oa) : 0u, a2 = oa >= 0 ? ph[3 * oa + 2] : 0u;
+                    uint32_t b0 = ob >= 0 ? rg(ob) : 0u, b2 = ob >= 0 ? ph[3 * ob + 2] : 0u;
+                    uint32_t c0 = oc >= 0 ? rg(oc) : 0u, c2 = oc >= 0 ? ph[3 * oc + 2] : 0u;
+                    uint32_t d0 = od >= 0 ? rg(od) : 0u, d2 = od >= 0 ? ph[3 * od + 2] : 0u;
+                    wi_taps_read(a0, a2, b0, b2, c0, c2, d0, d2);
+                    ra = wi_luma(a0 & 255u, a0 >> 8, a2); rb = wi_luma(b0 & 255u, b0 >> 8, b2);
+                    rc = wi_luma(c0 & 255u, c0 >> 8, c2); rd = wi_luma(d0 & 255u, d0 >> 8, d2);
+                }
+            } else {
+                const PIX* pl = img + ch * cs;
+                // (the four reads, then the decode of a byte set's taps: wi_taps_read)
+                using RAW = decltype(wi_raw(pl[0]));
+                RAW qa = LDS_IMG || oa >= 0 ? wi_raw(pl[ia]) : RAW(0), qb = LDS_IMG || ob >= 0 ? wi_raw(pl[ib]) : RAW(0);
+                RAW qc = LDS_IMG || oc >= 0 ? wi_raw(pl[ic]) : RAW(0), qd = LDS_IMG || od >= 0 ? wi_raw(pl[id]) : RAW(0);
+                wi_taps_read(qa, qb, qc, qd);
+                ra = wi_pix(qa); rb = wi_pix(qb); rc = wi_pix(qc); rd = wi_pix(qd);
+            }
             const float a = oa >= 0 ? ra : 0.f, b = ob >= 0 ? rb : 0.f, cc = oc >= 0 ? rc : 0.f, d = od >= 0 ? rd : 0.f;
             const float top = a + (b - a) * fx, bot = cc + (d - cc) * fx;
             float v = top + (bot - top) * fy;
@@ -300,7 +414,8 @@ __global__ __launch_bounds__(256) void warp_images_kernel(const PIX* __restrict_
         for (int e = tid; e < Eo; e += 256) o[e] = gi_nan();
         return;
     }
-    wi_load(set + (long long)i * E, img, E, vec, tid);
+    if constexpr (wi_is_luma<PIX>::value) wi_load_luma<SET_NCHW>(&set->b + 3 * ((long long)i * E), img, E, vec, tid);     // (c == 1: E pixels)
+    else wi_load(set + (long long)i * E, img, E, vec, tid);
     // (the barrier inside wi_warp: the image is complete before the first tap)
     wi_warp<SET_NCHW>(img, mats, gains, j, c, hs, ws, ho, wo, edge, tid,
                       [&](int p, int ch, float v) { o[OUT_NCHW ? ch * Po + p : p * c + ch] = v; });
@@ -335,6 +450,24 @@ int fg_launch_warp_images_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, i
                        ho, wo, out, edge, vec)
     FG_BY_LAYOUT(set_nchw, out_nchw, IMAGES_U8)
 #undef IMAGES_U8
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
+// fg_warp_images_u8_y: a set of R, G, B bytes read as luma, one channel out: fg_launch_warp_images' grid, block and LDS at c == 1
+// (the block's copy holds the hs * ws luma floats).  An instance per set layout (the batch's two layouts are one order); `vec`
+// carries wi_wide_u8_y
+int fg_launch_warp_images_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                               const float* gains, int n, float* out, int ho, int wo, int edge) {
+    const int P = hs * ws;
+    const size_t lds = ((size_t)P * sizeof(float) + 15) & ~(size_t)15;
+    const int vec = wi_wide_u8_y(set, P);
+    const dim3 images((unsigned)n);
+    const wi_y8* luma = reinterpret_cast<const wi_y8*>(set);
+#define IMAGES_Y(SN, ON)                                                                                                         \
+    hipLaunchKernelGGL((warp_images_kernel<SN, ON, wi_y8>), images, dim3(256), lds, ctx->stream, luma, n_set, idx, mats, gains, 1, hs, ws, \
+                       ho, wo, out, edge, vec)
+    if (set_nchw) { IMAGES_Y(true, true); } else { IMAGES_Y(false, true); }
+#undef IMAGES_Y
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }
@@ -415,7 +548,8 @@ __global__ __launch_bounds__(256) void warp_c2f_kernel(const PIX* __restrict__ s
     if (diff) diff += base;
     const int i = idx[j];
     if (i < 0 || (long long)i >= n_set) { c2f_fill_nan(fine, coarse, diff, Eo, tid); return; }
-    wi_load(set + (long long)i * E, A, E, vec, tid);
+    if constexpr (wi_is_luma<PIX>::value) wi_load_luma<SET_NCHW>(&set->b + 3 * ((long long)i * E), A, E, vec, tid);       // (c == 1: E pixels)
+    else wi_load(set + (long long)i * E, A, E, vec, tid);
     for (int k = tid; k < s + cs; k += 256) T[k] = k < s ? fg_scale_plan(cs, s, k) : fg_scale_plan(s, cs, k - s);
     // (the barrier inside wi_warp: the image is complete before the first tap, and the plans before the passes below)
     wi_warp<SET_NCHW>(A, mats, gains, j, c, hs, ws, s, s, edge, tid, [&](int p, int ch, float v) { B[ch * Po + p] = v; });
@@ -468,6 +602,27 @@ int fg_launch_warp_c2f_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int 
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }
+// fg_warp_c2f_u8_y: fg_launch_warp_c2f's grid, block and LDS at c == 1; the two luma instances have their limit raised behind
+// their own keys
+int fg_launch_warp_c2f_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                            const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int edge) {
+    const int P = hs * ws, Pc = cs * cs;
+    const size_t lds = (((size_t)(((P > Pc ? P : Pc) + 3) & ~3) + (size_t)s * s) * sizeof(float) + (size_t)(s + cs) * sizeof(ScaleTerm) + 15) & ~(size_t)15;
+    const int vec = wi_wide_u8_y(set, P);
+    const dim3 images((unsigned)n);
+    const wi_y8* luma = reinterpret_cast<const wi_y8*>(set);
+#define C2F_Y(SN, ON)                                                                                                            \
+    static char attr_key;                                                                                                        \
+    if (fg_attr_first(ctx, &attr_key))                                                                                           \
+        FG_HIP(ctx, hipFuncSetAttribute((const void*)warp_c2f_kernel<SN, ON, wi_y8>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                        (int)(2 * FG_WARP_MAX_FLOATS * sizeof(float) + 2 * 128 * sizeof(ScaleTerm))));           \
+    hipLaunchKernelGGL((warp_c2f_kernel<SN, ON, wi_y8>), images, dim3(256), lds, ctx->stream, luma, n_set, idx, mats, gains, 1, hs, ws, s, \
+                       cs, fine, coarse, diff, edge, vec)
+    if (set_nchw) { C2F_Y(true, true); } else { C2F_Y(false, true); }
+#undef C2F_Y
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
 // fg_warp_faces (include/facegen_hip.h): the reference's pipeline on a photo of any size.  The photo stays in global memory: wi_warp
 // takes the four taps of every channel of a window pixel straight from it (lanes on neighbouring window pixels read neighbouring
 // addresses of a channel-major photo; a pixel's c floats are adjacent in a pixel-major one) and stores the hw x ww window into A,
@@ -492,7 +647,7 @@ __global__ __launch_bounds__(256) void warp_faces_kernel(const PIX* __restrict__
     if (diff) diff += base;
     const int i = idx[j];
     if (i < 0 || (long long)i >= n_set) { c2f_fill_nan(fine, coarse, diff, Eo, tid); return; }
-    const PIX* photo = set + (long long)i * ((long long)c * hs * ws);
+    const PIX* photo = set + (long long)i * ((long long)(wi_is_luma<PIX>::value ? 3 : c) * hs * ws);       // (a luma set: c == 1 of 3 bytes)
     for (int k = tid; k < 3 * s + cs; k += 256)
         T[k] = k < s ? fg_scale_plan(cs, s, k) : k < s + cs ? fg_scale_plan(s, cs, k - s)
              : k < 2 * s + cs ? fg_scale_plan(ww, s, k - s - cs) : fg_scale_plan(hw, s, k - 2 * s - cs);
@@ -564,6 +719,25 @@ int fg_launch_warp_faces_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, in
                        hw, ww, s, cs, fine, coarse, diff, edge)
     FG_BY_LAYOUT(set_nchw, out_nchw, FACES_U8)
 #undef FACES_U8
+    FG_CHECK_LAUNCH(ctx);
+    return FG_OK;
+}
+// fg_warp_faces_u8_y: fg_launch_warp_faces' grid, block and LDS at c == 1; the taps read the R, G, B bytes of a pixel one by one, so
+// any base will do
+int fg_launch_warp_faces_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_nchw, const int* idx, const float* mats,
+                              const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int edge) {
+    const size_t lds = fg_warp_faces_lds_bytes(1, hw, ww, s, cs);
+    const dim3 images((unsigned)n);
+    const wi_y8* luma = reinterpret_cast<const wi_y8*>(set);
+#define FACES_Y(SN, ON)                                                                                                          \
+    static char attr_key;                                                                                                        \
+    if (fg_attr_first(ctx, &attr_key))                                                                                           \
+        FG_HIP(ctx, hipFuncSetAttribute((const void*)warp_faces_kernel<SN, ON, wi_y8>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                        (int)FG_FACES_MAX_LDS));                                                                 \
+    hipLaunchKernelGGL((warp_faces_kernel<SN, ON, wi_y8>), images, dim3(256), lds, ctx->stream, luma, n_set, idx, mats, gains, 1, hs, ws, \
+                       hw, ww, s, cs, fine, coarse, diff, edge)
+    if (set_nchw) { FACES_Y(true, true); } else { FACES_Y(false, true); }
+#undef FACES_Y
     FG_CHECK_LAUNCH(ctx);
     return FG_OK;
 }

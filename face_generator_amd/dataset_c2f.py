@@ -171,21 +171,22 @@ class AugmentedResult(_PerPullResult):
             return tuple(self.ctx.empty(*shape) for _ in fields)
         both = self.augment.draw_device(self.ctx, n, (ds.h, ds.w))
         return ops.warp_c2f(ds.images, idx, s, self.coarseScale, mats=both[:6 * n], gains=both[6 * n:], fields=fields, set_layout="nchw",
-                            out_layout=layout, fill=self.augment.fill, ctx=self.ctx)
+                            out_layout=layout, fill=self.augment.fill, ctx=self.ctx, gray=ds.gray and ds.storage == "u8")
 
 
-def toResultAugmented(fineImages, coarseScale, fineScale, augment, ctx=None, storage="f32"):
+def toResultAugmented(fineImages, coarseScale, fineScale, augment, ctx=None, storage="f32", gray=False):
     """toResult for training on freshly augmented faces: fineImages (host or device [N, C, H, W] with H, W >= fineScale, or a
     DeviceDataset without an augmenter) is uploaded once and stays un-augmented in HBM; `augment`, an Augmenter whose out_hw is
     (fineScale, fineScale), draws the transforms of every pull -> AugmentedResult.  storage: DeviceDataset's ("u8": uint8 images
-    stay bytes in HBM, pixels of value b / 255); a DeviceDataset keeps its own."""
+    stay bytes in HBM, pixels of value b / 255) and gray (images of 3 channels, examples of their luma: one channel; with "u8"
+    every pull is one launch of fg_warp_c2f_u8_y on the R, G, B bytes); a DeviceDataset keeps its own."""
     from .runtime import get_context, DeviceDataset, FgError
     ctx = ctx or get_context()
     if not isinstance(fineImages, DeviceDataset):
         fine = torch.as_tensor(fineImages)
         if fine.dim() != 4 or fine.shape[-1] < fineScale or fine.shape[-2] < fineScale:
             raise ValueError("toResultAugmented: fine images must be [N, C, H, W] with H, W >= %d" % fineScale)
-        fineImages = DeviceDataset(ctx, fine, storage=storage)
+        fineImages = DeviceDataset(ctx, fine, storage=storage, gray=gray)
     elif fineImages.augment is not None:
         raise FgError("toResultAugmented: hand the Augmenter over as augment=, not on the DeviceDataset")
     return AugmentedResult(fineImages, coarseScale, fineScale, augment)
@@ -217,11 +218,12 @@ class PhotoResult(_PerPullResult):
         return self.set.gather_fields(indices, self._fields(fields), coarse_scale=self.coarseScale, layout=layout)
 
 
-def toResultPhotos(photos, window_hw, coarseScale, fineScale, augment, ctx=None, storage="f32"):
+def toResultPhotos(photos, window_hw, coarseScale, fineScale, augment, ctx=None, storage="f32", gray=False):
     """toResult for training on faces cut from whole photos under fresh transforms: photos (host or device [N, C, H, W], any H and
     W, or a runtime.PhotoDataset, which then carries window, fine scale and augmenter itself) is uploaded once and stays in HBM;
     `augment`, an Augmenter whose out_hw is window_hw (or None: the central window, un-augmented), draws the transforms of every
-    pull -> PhotoResult.  storage: PhotoDataset's ("u8": uint8 photos stay bytes in HBM, pixels of value b / 255); a PhotoDataset
+    pull -> PhotoResult.  storage: PhotoDataset's ("u8": uint8 photos stay bytes in HBM, pixels of value b / 255) and gray (photos
+    of 3 channels, examples of their luma: one channel; with "u8" every pull is one launch of fg_warp_faces_u8_y); a PhotoDataset
     keeps its own."""
     from .runtime import get_context, PhotoDataset, FgError
     if isinstance(photos, PhotoDataset):
@@ -230,7 +232,8 @@ def toResultPhotos(photos, window_hw, coarseScale, fineScale, augment, ctx=None,
         if photos.h != int(fineScale) or photos.window_hw != tuple(window_hw if not isinstance(window_hw, int) else (window_hw, window_hw)):
             raise FgError("toResultPhotos: the PhotoDataset hands out %dx%d faces of a %dx%d window" % ((photos.h, photos.w) + photos.window_hw))
         return PhotoResult(photos, coarseScale)
-    return PhotoResult(PhotoDataset(ctx or get_context(), photos, window_hw, int(fineScale), augment=augment, storage=storage), coarseScale)
+    return PhotoResult(PhotoDataset(ctx or get_context(), photos, window_hw, int(fineScale), augment=augment, storage=storage, gray=gray),
+                       coarseScale)
 
 
 def toResultDevice(fine_nhwc, coarseScale, ctx=None):

@@ -189,13 +189,25 @@ def _warp_entry(ctx, name, images):
     return getattr(ctx.lib, name + "_u8" if images.dtype == torch.uint8 else name)
 
 
+def _gray_channels(name, images, C, gray):
+    """the channels a warp hands out: the set's, or with gray=True the one luma channel of a uint8 set of 3 channels (the _u8_y
+    entries: Y = ((0.299f * p(r)) + (0.587f * p(g))) + (0.114f * p(b)), the same bits as the one-channel float set Y gives)"""
+    if not gray:
+        return C
+    if images.dtype != torch.uint8 or C != 3:
+        raise ValueError("%s: gray=True takes a uint8 set of 3 channels (the luma is formed from R, G, B bytes), got %s with %d -- "
+                         "convert a float set once instead" % (name, images.dtype, C))
+    return 1
+
+
 def warp_images(images, indices, mats=None, gains=None, out_hw=None, set_layout="nchw", out_layout="nhwc", fill="constant", out=None,
-                ctx=None):
+                ctx=None, gray=False):
     """out[j] = clamp01(gains[j] * bilinear(images[indices[j]], mats[j])): include/facegen_hip.h fg_warp_images.  images: device
     [N][C][H][W] (set_layout "nchw") or [N][H][W][C], float32 or uint8 (pixels of value b / 255: fg_warp_images_u8, the same bits as
     the float set b / 255 gives; warp_c2f and warp_faces likewise); indices: device int32 [n]; mats: device float32 [n][6] (output pixel ->
     source pixel) or None, the identity; gains: device float32 [n] or None (gain 1, no clamp); out_hw: (ho, wo), default the set's;
-    fill: "constant" (0 outside the image) or "edge".  -> device [n][ho][wo][C] ("nhwc") or [n][C][ho][wo]."""
+    fill: "constant" (0 outside the image) or "edge".  -> device [n][ho][wo][C] ("nhwc") or [n][C][ho][wo].  gray=True (a uint8
+    set of 3 channels; warp_c2f and warp_faces likewise): the luma of the R, G, B bytes, one channel out (fg_warp_images_u8_y)."""
     ctx = ctx or get_context()
     layouts, fills = {"nhwc": 0, "nchw": 1}, {"constant": 0, "edge": 1}
     if set_layout not in layouts or out_layout not in layouts or fill not in fills:
@@ -206,6 +218,7 @@ def warp_images(images, indices, mats=None, gains=None, out_hw=None, set_layout=
         N, C, H, W = images.shape
     else:
         N, H, W, C = images.shape
+    Cs, C = C, _gray_channels("warp_images", images, C, gray)
     ho, wo = (H, W) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
     if indices.dtype != torch.int32 or indices.dim() != 1 or not indices.is_contiguous():
         raise ValueError("warp_images: indices must be a contiguous 1-d int32 tensor")
@@ -221,15 +234,19 @@ def warp_images(images, indices, mats=None, gains=None, out_hw=None, set_layout=
     for name, t in (("images", images), ("indices", indices), ("mats", mats), ("gains", gains), ("out", out)):
         if t is not None and t.device != ctx.device:
             raise ValueError("warp_images: %s lives on %s, the context on %s" % (name, t.device, ctx.device))
-    if n:                                   # (an empty tensor has no address to hand over)
-        ctx.check(_warp_entry(ctx, "fg_warp_images", images)(ctx.h, images.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
+    if n and gray:
+        ctx.check(ctx.lib.fg_warp_images_u8_y(ctx.h, images.data_ptr(), N, H, W, layouts[set_layout], indices.data_ptr(),
+                                              None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n,
+                                              out.data_ptr(), ho, wo, fills[fill]))
+    elif n:                                 # (an empty tensor has no address to hand over)
+        ctx.check(_warp_entry(ctx, "fg_warp_images", images)(ctx.h, images.data_ptr(), N, Cs, H, W, layouts[set_layout], indices.data_ptr(),
                                          None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n,
                                          out.data_ptr(), ho, wo, layouts[out_layout], fills[fill]))
     return out.view(*shape)
 
 
 def warp_c2f(images, indices, fine_scale, coarse_scale, mats=None, gains=None, fields=("fine", "coarse", "diff"), set_layout="nchw",
-             out_layout="nhwc", fill="constant", ctx=None):
+             out_layout="nhwc", fill="constant", ctx=None, gray=False):
     """The c2f example of images[indices[j]] under mats[j] / gains[j] in one launch: include/facegen_hip.h fg_warp_c2f.  With F =
     warp_images(.., out_hw=(fine_scale, fine_scale)): fine = F, coarse = scale(scale(F, coarse_scale), fine_scale), diff = F -
     coarse.  images, indices, mats, gains, the layouts and fill as warp_images; fields: the outputs wanted, a subset of ("fine",
@@ -248,6 +265,7 @@ def warp_c2f(images, indices, fine_scale, coarse_scale, mats=None, gains=None, f
         N, C, H, W = images.shape
     else:
         N, H, W, C = images.shape
+    Cs, C = C, _gray_channels("warp_c2f", images, C, gray)
     s, cs = int(fine_scale), int(coarse_scale)
     if indices.dtype != torch.int32 or indices.dim() != 1 or not indices.is_contiguous():
         raise ValueError("warp_c2f: indices must be a contiguous 1-d int32 tensor")
@@ -261,15 +279,19 @@ def warp_c2f(images, indices, fine_scale, coarse_scale, mats=None, gains=None, f
     shape = (n, C, s, s) if layouts[out_layout] else (n, s, s, C)
     out = {f: ctx.empty(*shape) for f in fields}
     P = lambda f: out[f].data_ptr() if f in out else None
-    if n:                                   # (an empty tensor has no address to hand over)
-        ctx.check(_warp_entry(ctx, "fg_warp_c2f", images)(ctx.h, images.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
+    if n and gray:
+        ctx.check(ctx.lib.fg_warp_c2f_u8_y(ctx.h, images.data_ptr(), N, H, W, layouts[set_layout], indices.data_ptr(),
+                                           None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n, s, cs,
+                                           P("fine"), P("coarse"), P("diff"), fills[fill]))
+    elif n:                                 # (an empty tensor has no address to hand over)
+        ctx.check(_warp_entry(ctx, "fg_warp_c2f", images)(ctx.h, images.data_ptr(), N, Cs, H, W, layouts[set_layout], indices.data_ptr(),
                                       None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n, s, cs,
                                       P("fine"), P("coarse"), P("diff"), layouts[out_layout], fills[fill]))
     return tuple(out[f] for f in fields)
 
 
 def warp_faces(photos, indices, window_hw, s, cs=0, mats=None, gains=None, fields=("fine",), set_layout="nchw", out_layout="nhwc",
-               fill="constant", out=None, ctx=None):
+               fill="constant", out=None, ctx=None, gray=False):
     """The faces of photos[indices[j]] under mats[j] / gains[j] in one launch: include/facegen_hip.h fg_warp_faces.  The photos may
     have any size: W = warp_images(.., out_hw=window_hw) in photo coordinates, fine = scale(W, s, s) and, with cs > 0, coarse =
     scale(scale(fine, cs), s), diff = fine - coarse.  photos, indices, mats, gains, the layouts and fill as warp_images; fields:
@@ -290,6 +312,7 @@ def warp_faces(photos, indices, window_hw, s, cs=0, mats=None, gains=None, field
         N, C, H, W = photos.shape
     else:
         N, H, W, C = photos.shape
+    Cs, C = C, _gray_channels("warp_faces", photos, C, gray)
     hw, ww = int(window_hw[0]), int(window_hw[1])
     if indices.dtype != torch.int32 or indices.dim() != 1 or not indices.is_contiguous():
         raise ValueError("warp_faces: indices must be a contiguous 1-d int32 tensor")
@@ -305,8 +328,12 @@ def warp_faces(photos, indices, window_hw, s, cs=0, mats=None, gains=None, field
             raise ValueError("warp_faces: %s lives on %s, the context on %s" % (name, t.device, ctx.device))
     res = {f: ctx.empty(*shape) if out is None else out.view(*shape) for f in fields}
     P = lambda f: res[f].data_ptr() if f in res else None
-    if n:                                   # (an empty tensor has no address to hand over)
-        ctx.check(_warp_entry(ctx, "fg_warp_faces", photos)(ctx.h, photos.data_ptr(), N, C, H, W, layouts[set_layout], indices.data_ptr(),
+    if n and gray:
+        ctx.check(ctx.lib.fg_warp_faces_u8_y(ctx.h, photos.data_ptr(), N, H, W, layouts[set_layout], indices.data_ptr(),
+                                             None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n, hw, ww,
+                                             s, cs, P("fine"), P("coarse"), P("diff"), fills[fill]))
+    elif n:                                 # (an empty tensor has no address to hand over)
+        ctx.check(_warp_entry(ctx, "fg_warp_faces", photos)(ctx.h, photos.data_ptr(), N, Cs, H, W, layouts[set_layout], indices.data_ptr(),
                                         None if mats is None else mats.data_ptr(), None if gains is None else gains.data_ptr(), n, hw, ww,
                                         s, cs, P("fine"), P("coarse"), P("diff"), layouts[out_layout], fills[fill]))
     return tuple(res[f] for f in fields)

@@ -732,19 +732,41 @@ def is_resident(dataset):
     return not torch.is_tensor(dataset) and callable(getattr(dataset, "gather", None))
 
 
-def _resident_pixels(cls, ctx, images, storage, what):
+LUMA = (0.299, 0.587, 0.114)                 # image.rgb2y: Y = ((0.299f * R) + (0.587f * G)) + (0.114f * B), include/facegen_hip.h
+
+
+def _luma_f32(ctx, x, rows=256):
+    """[N][3][H][W] of any dtype -> device float32 [N][1][H][W], Y of the float32 pixels: every product and sum a float32 operation
+    of its own, in the header's order (what the _u8_y entries form from bytes).  Done once per set, `rows` images at a time, so
+    that the three-channel floats never lie in HBM whole"""
+    k = torch.tensor(LUMA, dtype=torch.float32, device=ctx.device)
+    y = torch.empty((x.shape[0], 1) + tuple(x.shape[2:]), dtype=torch.float32, device=ctx.device)
+    for lo in range(0, x.shape[0], rows):
+        f = x[lo:lo + rows].to(dtype=torch.float32).to(ctx.device)
+        y[lo:lo + rows, 0] = (f[:, 0] * k[0] + f[:, 1] * k[1]) + f[:, 2] * k[2]
+    return y
+
+
+def _resident_pixels(cls, ctx, images, storage, what, gray=False):
     """the images of a resident set as they are kept in HBM (cls: the class named in the messages).  storage "f32": float32, any
     input converted as torch converts it (a uint8 pixel b becomes the float b); "u8": the bytes of a uint8 input, kept as bytes --
-    a pixel b has the value b / 255 and is decoded where the warps read it (include/facegen_hip.h, the _u8 entries)"""
+    a pixel b has the value b / 255 and is decoded where the warps read it (include/facegen_hip.h, the _u8 entries).  gray: the
+    input has 3 channels and the set hands out their luma, one channel (the reference's --grayscale, dataset.lua:90): "f32" keeps
+    the luma, converted here once (_luma_f32); "u8" keeps the R, G, B bytes, and the warps form the luma where they read them
+    (the _u8_y entries)"""
     if storage not in ("f32", "u8"):
         raise FgError("%s: storage is 'f32' or 'u8', got %r" % (cls, storage))
     x = torch.as_tensor(images)
     if x.dim() != 4 or x.shape[0] < 1:
         raise FgError("%s: %s must be [N][C][H][W] with N >= 1, got %s" % (cls, what, tuple(x.shape)))
+    if gray and x.shape[1] != 3:
+        raise FgError("%s: gray=True forms the luma of R, G, B: %s must have 3 channels, got %d" % (cls, what, x.shape[1]))
     if storage == "u8":
         if x.dtype != torch.uint8:
             raise FgError("%s: storage='u8' keeps the bytes of a uint8 input, got %s" % (cls, x.dtype))
         return x.to(ctx.device).contiguous()
+    if gray:
+        return _luma_f32(ctx, x)
     return x.to(dtype=torch.float32).to(ctx.device).contiguous()
 
 
@@ -769,22 +791,32 @@ class DeviceDataset:
     storage="u8" keeps a uint8 set as bytes in HBM, a quarter of the float set: a pixel b has the value b / 255, the float the host
     loaders make of a JPEG's byte, and every pull decodes it in the launch that reads it (fg_warp_images_u8; the un-augmented
     gather is its identity call, so images above 16384 pixels are refused there).  Every float handed out -- gather, rows, ds[i] --
-    is bit for bit the one the float set b / 255 gives."""
+    is bit for bit the one the float set b / 255 gives.
 
-    def __init__(self, ctx, images, scale=None, augment=None, storage="f32"):
+    gray=True takes images of 3 channels and hands out their luma (the reference's --grayscale: image.load(path, 1, "float"),
+    dataset.lua:90): the set reports c == 1, what it hands out, and set_c == 3.  With storage="f32" the luma is formed once, here,
+    and the set is an ordinary one-channel set from then on (scale= runs on the luma: dataset.lua:90 before :95).  With
+    storage="u8" the set stays the R, G, B bytes -- a luma pixel is no byte -- and every pull is one launch of
+    fg_warp_images_u8_y, bit for bit what the float luma set gives."""
+
+    def __init__(self, ctx, images, scale=None, augment=None, storage="f32", gray=False):
         """images: host or device [N][C][H][W], tensor or array: float32, or uint8 with storage="u8".  scale: side to scale every
         image to on the device (image.scale, dataset.lua:95) when H, W differ from it; not with storage="u8" (a scaled image is no
         longer 8-bit).  augment: an Augmenter for gather(), see set_augment()."""
-        self.ctx, self.lib, self.storage = ctx, ctx.lib, storage
+        self.ctx, self.lib, self.storage, self.gray = ctx, ctx.lib, storage, bool(gray)
         self.set_augment(augment)
         if storage == "u8" and scale is not None:
             raise FgError("DeviceDataset: storage='u8' takes no scale=, a scaled image is no longer 8-bit")
-        x = _resident_pixels("DeviceDataset", ctx, images, storage, "images")
+        x = _resident_pixels("DeviceDataset", ctx, images, storage, "images", gray=self.gray)
         if scale is not None and (x.shape[2] != scale or x.shape[3] != scale):
             from . import ops
             x = ops.scale_bilinear(x, int(scale), int(scale), layout="nchw", ctx=ctx)
         self.images = x
         self.n, self.c, self.h, self.w = (int(v) for v in x.shape)
+        self.set_c = 3 if self.gray else self.c                             # the channels of the input; c: of what is handed out
+        self._luma = self.gray and storage == "u8"                          # R, G, B bytes in HBM, read as luma
+        if self._luma:
+            self.c = 1
 
     def size(self):
         return self.n
@@ -833,7 +865,10 @@ class DeviceDataset:
             out = self.ctx.empty(*shape)
         elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * self.c * self.h * self.w:
             raise FgError("DeviceDataset.gather: out must be a contiguous float32 tensor of %d elements" % (n * self.c * self.h * self.w))
-        if n and self.storage == "u8":      # the identity call: fg_gather_images' bits, decoded (no matrices, no gains)
+        if n and self._luma:                # the identity call of the luma entry
+            self.ctx.check(self.lib.fg_warp_images_u8_y(self.ctx.h, self.images.data_ptr(), self.n, self.h, self.w, 1, idx.data_ptr(), None, None,
+                                                        n, out.data_ptr(), self.h, self.w, 0))
+        elif n and self.storage == "u8":    # the identity call: fg_gather_images' bits, decoded (no matrices, no gains)
             self.ctx.check(self.lib.fg_warp_images_u8(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1, idx.data_ptr(),
                                                       None, None, n, out.data_ptr(), self.h, self.w, 0 if layout == "nhwc" else 1, 0))
         elif n:                             # (an empty tensor has no address to hand over)
@@ -853,9 +888,13 @@ class DeviceDataset:
             raise FgError("DeviceDataset.gather: out must be a contiguous float32 tensor of %d elements" % (n * self.c * ho * wo))
         if n:
             both = aug.draw_device(self.ctx, n, (self.h, self.w))
-            warp = self.lib.fg_warp_images_u8 if self.storage == "u8" else self.lib.fg_warp_images
-            self.ctx.check(warp(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1, idx.data_ptr(), both.data_ptr(),
-                                both.data_ptr() + 24 * n, n, out.data_ptr(), ho, wo, 0 if layout == "nhwc" else 1, aug.fill_code))
+            if self._luma:
+                self.ctx.check(self.lib.fg_warp_images_u8_y(self.ctx.h, self.images.data_ptr(), self.n, self.h, self.w, 1, idx.data_ptr(),
+                                                            both.data_ptr(), both.data_ptr() + 24 * n, n, out.data_ptr(), ho, wo, aug.fill_code))
+            else:
+                warp = self.lib.fg_warp_images_u8 if self.storage == "u8" else self.lib.fg_warp_images
+                self.ctx.check(warp(self.ctx.h, self.images.data_ptr(), self.n, self.c, self.h, self.w, 1, idx.data_ptr(), both.data_ptr(),
+                                    both.data_ptr() + 24 * n, n, out.data_ptr(), ho, wo, 0 if layout == "nhwc" else 1, aug.fill_code))
         return out.view(*shape)
 
 
@@ -1029,11 +1068,17 @@ class PhotoDataset:
     The dataset protocol is DeviceDataset's: size(), len(), ds[i] -> the host CHW face of the central window under the identity,
     indices(), rows(), gather(); is_resident() is true for it."""
 
-    def __init__(self, ctx, photos, window_hw, out_hw, augment=None, storage="f32"):
-        """storage="u8": uint8 photos stay bytes in HBM, a pixel b has the value b / 255 (fg_warp_faces_u8), as DeviceDataset's"""
-        self.ctx, self.lib, self.storage = ctx, ctx.lib, storage
-        self.photos = _resident_pixels("PhotoDataset", ctx, photos, storage, "photos")
+    def __init__(self, ctx, photos, window_hw, out_hw, augment=None, storage="f32", gray=False):
+        """storage="u8": uint8 photos stay bytes in HBM, a pixel b has the value b / 255 (fg_warp_faces_u8), as DeviceDataset's.
+        gray=True: photos of 3 channels, faces of their luma (c == 1, set_c == 3), as DeviceDataset's: "f32" keeps the luma, formed
+        once; "u8" keeps the R, G, B bytes and every pull is one launch of fg_warp_faces_u8_y"""
+        self.ctx, self.lib, self.storage, self.gray = ctx, ctx.lib, storage, bool(gray)
+        self.photos = _resident_pixels("PhotoDataset", ctx, photos, storage, "photos", gray=self.gray)
         self.n, self.c, self.photo_h, self.photo_w = (int(v) for v in self.photos.shape)
+        self.set_c = 3 if self.gray else self.c
+        self._luma = self.gray and storage == "u8"
+        if self._luma:
+            self.c = 1
         self.window_hw = (int(window_hw), int(window_hw)) if isinstance(window_hw, int) else (int(window_hw[0]), int(window_hw[1]))
         sides = (out_hw, out_hw) if isinstance(out_hw, int) else tuple(out_hw)
         if len(sides) != 2 or int(sides[0]) != int(sides[1]) or int(sides[0]) < 1:
@@ -1095,7 +1140,7 @@ class PhotoDataset:
         mats, gains, fill = self.transforms(n, augment) if n else (None, None, "constant")
         try:
             return ops.warp_faces(self.photos, idx, self.window_hw, self.h, coarse_scale, mats=mats, gains=gains, fields=fields,
-                                  set_layout="nchw", out_layout=layout, fill=fill, out=out, ctx=self.ctx)
+                                  set_layout="nchw", out_layout=layout, fill=fill, out=out, ctx=self.ctx, gray=self._luma)
         except ValueError as e:
             raise FgError("PhotoDataset.gather: %s" % e)
 

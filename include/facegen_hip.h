@@ -674,6 +674,50 @@ int fg_warp_faces_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, in
                      const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff,
                      int out_layout, int fill);
 
+/* ---- grayscale from a resident byte set: the three warps on a set of R, G, B bytes read as luma.  The reference's grayscale mode
+ *      (th train.lua --grayscale) loads every picture with image.load(path, 1, "float") (dataset.lua:90), the luma of the JPEG's RGB
+ *      bytes, and scales that one channel (:95).  A luma pixel is no byte (for gray triples r = g = b it equals p(b) for only 191 of
+ *      the 256 bytes), so the set stays the RGB bytes -- exact, and the one resident set serves colour and grayscale runs -- and the
+ *      luma is formed where the bytes are read. ----
+ * set: n_set images of 3 * hs * ws device bytes in set_layout: 0, pixel-major (the R, G, B of a pixel adjacent), or 1, three planes
+ *   R, G, B of hs * ws bytes.  There is no c: three channels in, one out; the batch has one channel, its two layouts are one order,
+ *   so there is no out_layout.  With p(b) = (float)b / 255.0f as above, the value of a pixel is
+ *     Y(r, g, b) = ((0.299f * p(r)) + (0.587f * p(g))) + (0.114f * p(b))
+ *   in fp32, every product and sum rounded on its own in this order (no FMA contraction); the three constants are the floats
+ *   nearest to the decimals, 0x1.322d0ep-2, 0x1.2c8b44p-1, 0x1.d2f1aap-4.  This is Torch7's image.rgb2y on a float tensor
+ *   (output:zero():add(0.299, R):add(0.587, G):add(0.114, B)); like the rest of the `image` package it is un-vendored: parity
+ *   unpinned by the reference.  Y <= 1.0 for all 256^3 triples and white is exactly 1.0; the sum evaluated in double and rounded once
+ *   is another float for 30 % of the triples.
+ * Bits: every float a _u8_y entry writes equals, bit for bit, what its fp32 sibling (fg_warp_images, fg_warp_c2f, fg_warp_faces)
+ *   writes with c = 1 for the float set Y(set) and the same other arguments: both fills, mats and gains NULL or given, every subset
+ *   of fine / coarse / diff.  With mats == NULL and gains == NULL the entries decode: out[j] = Y(set[idx[j]]).
+ * Everything else is the sibling's contract at c = 1: the refusals and their codes (a message names the _u8_y entry), an idx[j]
+ *   outside [0, n_set) reads nothing and gives a quiet-NaN image (0x7fc00000) in every requested output, repeated indices, the
+ *   64-bit base offset of an image, n == 0 (FG_OK without a launch), the NULL rules, cs <= s, a layout or fill other than 0 / 1 is
+ *   FG_ERR_INVALID; nothing written outside the requested outputs; one launch on the context's stream, grid n, block 256, the LDS
+ *   size of the sibling at c = 1, no scratch, no atomics, no synchronisation.
+ * Limits, counted in luma floats: hs * ws <= 16384 for fg_warp_images_u8_y and fg_warp_c2f_u8_y (the block's copy in LDS holds the
+ *   luma, a third of the image: sources up to 128 x 128, where three channels top out at 73 x 73), s * s <= 16384 for
+ *   fg_warp_c2f_u8_y; fg_warp_faces_u8_y takes photos of any size below 2^31 bytes (3 * hs * ws) under the LDS formula of
+ *   fg_warp_faces at c = 1.  Beyond these: FG_ERR_UNSUPPORTED with the size and the limit in the message; a photo of 2^31 bytes or
+ *   more is FG_ERR_INVALID, as the sibling's is (offsets inside a photo are 32-bit).
+ * Alignment: one byte is enough, for any base and any image size.  Nothing outside set[0 .. 3 * n_set * hs * ws) is read.  The copy
+ *   of the source image (fg_warp_images_u8_y, fg_warp_c2f_u8_y) chooses its loads on the host, for either layout by one rule: with
+ *   P = hs * ws, 16-byte loads only when `set` is 16-byte aligned and P % 16 == 0 (pixel-major: 3 P % 16 == 0, the same), 4-byte
+ *   loads only when `set` is 4-byte aligned and P % 4 == 0, byte loads otherwise.  Planes: a lane takes 16 / 4 / 1 pixels from each
+ *   of the three planes (the image's base 3 P i and the plane offsets P and 2 P are then aligned to the load); pixel-major: 16 / 4 /
+ *   1 pixels as three loads of 48 / 12 / 3 contiguous bytes (the compiler may join the narrower ones: 12 bytes in one load, 3 as
+ *   2 + 1).  No load reaches over the end of a plane or of an image.  fg_warp_faces_u8_y reads the twelve bytes of a window pixel
+ *   (R, G, B of the four taps) as single bytes from planes, and from triples as the 2 bytes R, G (at any address) and the byte B;
+ *   a tap outside the photo reads nothing. */
+int fg_warp_images_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_layout, const int* idx,
+                        const float* mats, const float* gains, int n, float* out, int ho, int wo, int fill);
+int fg_warp_c2f_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_layout, const int* idx,
+                     const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int fill);
+int fg_warp_faces_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_layout, const int* idx,
+                       const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff,
+                       int fill);
+
 /* ---- the random transforms of dataset/generate_dataset.py (:43-48 and its create_aug_matrices: flip, zoom, rotation, shear,
  *      translation, brightness) drawn, assembled into matrices and left on the device: the mats / gains of fg_warp_images and
  *      fg_warp_c2f for n images in one launch, no host arithmetic and no upload per batch. ----

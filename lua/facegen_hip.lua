@@ -154,6 +154,9 @@ int fg_warp_faces(fg_ctx* ctx, const float* set, long long n_set, int c, int hs,
 int fg_warp_images_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, float* out, int ho, int wo, int out_layout, int fill);
 int fg_warp_c2f_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill);
 int fg_warp_faces_u8(fg_ctx* ctx, const uint8_t* set, long long n_set, int c, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int out_layout, int fill);
+int fg_warp_images_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, float* out, int ho, int wo, int fill);
+int fg_warp_c2f_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int s, int cs, float* fine, float* coarse, float* diff, int fill);
+int fg_warp_faces_u8_y(fg_ctx* ctx, const uint8_t* set, long long n_set, int hs, int ws, int set_layout, const int* idx, const float* mats, const float* gains, int n, int hw, int ww, int s, int cs, float* fine, float* coarse, float* diff, int fill);
 typedef struct fg_augment_spec { int hflip, vflip; int zoom_equal; double zoom_lo, zoom_hi; int rot_lo, rot_hi; int shear_lo, shear_hi; int tx_lo, tx_hi, ty_lo, ty_hi; double gain_lo, gain_hi; } fg_augment_spec;
 int fg_draw_transforms(fg_ctx* ctx, const fg_augment_spec* spec, uint64_t seed, uint64_t offset, int n, int hs, int ws, int ho, int wo, float* mats, float* gains);
 int fg_scale_bilinear(fg_ctx* ctx, const float* src, float* dst, int n, int c, int hs, int ws, int hd, int wd, int layout);
@@ -814,7 +817,7 @@ function M.gatherImages(set, nSet, c, h, w, setLayout, idx, n, out, outLayout)
     check(C.fg_gather_images(ctx, set.ptr, nSet, c, h, w, setLayout, ffi.cast('const int*', idx.ptr), n, out.ptr, outLayout))
     return out
 end
--- FG.Dataset(images): a host FloatTensor [N][C][H][W], or FG.u8(a ByteTensor) of that shape (below), uploaded once.  It keeps dataset.lua's protocol -- ds:size(), ds[i] -> host CHW
+-- FG.Dataset(images): a host FloatTensor [N][C][H][W], or FG.u8(a ByteTensor) of that shape or FG.u8y(one of 3 channels) (below), uploaded once.  It keeps dataset.lua's protocol -- ds:size(), ds[i] -> host CHW
 -- FloatTensor (1-based, one small copy) -- and adds ds:gather(picks): the batch {ds[picks[1]], ...} as a device NHWC tensor, one launch
 local Dataset = {}
 Dataset.__index = function(self, k)
@@ -830,20 +833,31 @@ function M.u8(bytes)
     assert(torch.isTensor(bytes) and bytes:type() == 'torch.ByteTensor', 'FG.u8: a ByteTensor')
     return setmetatable({tensor = bytes}, U8)
 end
+-- FG.u8y(bytes): the option gray = true on top of FG.u8, handed over in the same places -- a ByteTensor [N][3][H][W] of R, G, B stays
+-- bytes in HBM and the set hands out the luma, one channel (the reference's --grayscale: image.load(path, 1, 'float'), dataset.lua:90):
+-- Y = ((0.299f * r / 255) + (0.587f * g / 255)) + (0.114f * b / 255), each operation rounded on its own, formed in the launch that reads
+-- the bytes (the fg_warp_*_u8_y entries).  Every float handed out is bit for bit the one the one-channel float set Y gives.  The set
+-- reports c == 1, what it hands out, and setC == 3
+function M.u8y(bytes)
+    assert(torch.isTensor(bytes) and bytes:type() == 'torch.ByteTensor', 'FG.u8y: a ByteTensor')
+    assert(bytes:dim() == 4 and bytes:size(2) == 3, 'FG.u8y: [N][3][H][W], the luma is formed from R, G, B')
+    return setmetatable({tensor = bytes, gray = true}, U8)
+end
 -- images or FG.u8(images) -> the host tensor, its copy in HBM (DeviceTensor; of bytes: padded to whole words, .bytes its typed pointer)
--- and the storage, 'f32' or 'u8'
+-- and the storage, 'f32', 'u8' or 'u8y' (FG.u8y: R, G, B bytes read as luma)
 local function residentPixels(images)
     if getmetatable(images) ~= U8 then return images, M.DeviceTensor(images:nElement()):copy(images:float()), 'f32' end
     local host = images.tensor:contiguous()
     local dev = M.DeviceTensor(math.ceil(host:nElement() / 4))
     check(C.fg_h2d(ctx, dev.ptr, host:data(), host:nElement()))
     dev.bytes = ffi.cast('const uint8_t*', dev.ptr)
-    return host, dev, 'u8'
+    return host, dev, images.gray and 'u8y' or 'u8'
 end
 function M.Dataset(images)
     local host, dev, storage = residentPixels(images)
     assert(host:dim() == 4 and host:size(1) >= 1, 'FG.Dataset: [N][C][H][W] with N >= 1')
-    return setmetatable({images = dev, n = host:size(1), c = host:size(2), h = host:size(3), w = host:size(4), storage = storage}, Dataset)
+    return setmetatable({images = dev, n = host:size(1), c = storage == 'u8y' and 1 or host:size(2), setC = host:size(2), h = host:size(3),
+                         w = host:size(4), storage = storage}, Dataset)
 end
 function M.isDataset(x) return type(x) == 'table' and getmetatable(x) == Dataset end
 function Dataset:size() return self.n end
@@ -851,7 +865,7 @@ function Dataset:get(i)
     assert(i >= 1 and i <= self.n, 'FG.Dataset: index out of range')
     local e = self.c * self.h * self.w
     local t = torch.FloatTensor(self.c, self.h, self.w)
-    if self.storage == 'u8' then                -- decoded by the identity launch, CHW
+    if self.storage ~= 'f32' then               -- decoded by the identity launch, CHW
         local image = self:gather({i}, 1, 1)
         check(C.fg_d2h(ctx, t:data(), image.ptr, e * 4))
     else
@@ -872,7 +886,7 @@ function Dataset:gather(picks, n, outLayout)
         idx = M.indexTensor(zero)
     end
     local out = M.DeviceTensor(n * self.c * self.h * self.w)
-    if self.storage == 'u8' then return self:gatherWarped(idx, n, nil, nil, out, outLayout or 0, 0), idx end     -- the identity call
+    if self.storage ~= 'f32' then return self:gatherWarped(idx, n, nil, nil, out, outLayout or 0, 0), idx end    -- the identity call
     return M.gatherImages(self.images, self.n, self.c, self.h, self.w, 1, idx, n, out, outLayout or 0), idx
 end
 -- fg_warp_images: out[j] = clamp01(gains[j] * bilinear(set[idx[j]], mats[j])), the augmentation of dataset/generate_dataset.py per batch.
@@ -887,6 +901,11 @@ end
 -- set's own size (a crop of a set with a margin: M.warpImages); idx: a DeviceTensor of 0-based int32 (M.indexTensor) with its count n
 function Dataset:gatherWarped(idx, n, mats, gains, out, outLayout, fill)
     out = out or M.DeviceTensor(n * self.c * self.h * self.w)
+    if self.storage == 'u8y' then               -- (one channel out: no c, no outLayout)
+        check(C.fg_warp_images_u8_y(ctx, self.images.bytes, self.n, self.h, self.w, 1, ffi.cast('const int*', idx.ptr),
+                                    mats and mats.ptr or nil, gains and gains.ptr or nil, n, out.ptr, self.h, self.w, fill or 0))
+        return out
+    end
     if self.storage == 'u8' then
         check(C.fg_warp_images_u8(ctx, self.images.bytes, self.n, self.c, self.h, self.w, 1, ffi.cast('const int*', idx.ptr),
                                   mats and mats.ptr or nil, gains and gains.ptr or nil, n, out.ptr, self.h, self.w, outLayout or 0, fill or 0))
@@ -909,6 +928,12 @@ end
 -- scale(scale(fine, cs, cs), s, s), diff = fine - coarse.  fine / coarse / diff: DeviceTensors of n * c * s * s floats in outLayout, or
 -- nil: not wanted, not written (at least one is given); idx, mats, gains, fill as ds:gatherWarped.  Returns fine, coarse, diff
 function Dataset:gatherWarpedC2F(idx, n, mats, gains, s, cs, fine, coarse, diff, outLayout, fill)
+    if self.storage == 'u8y' then
+        check(C.fg_warp_c2f_u8_y(ctx, self.images.bytes, self.n, self.h, self.w, 1, ffi.cast('const int*', idx.ptr),
+                                 mats and mats.ptr or nil, gains and gains.ptr or nil, n, s, cs, fine and fine.ptr or nil,
+                                 coarse and coarse.ptr or nil, diff and diff.ptr or nil, fill or 0))
+        return fine, coarse, diff
+    end
     if self.storage == 'u8' then
         check(C.fg_warp_c2f_u8(ctx, self.images.bytes, self.n, self.c, self.h, self.w, 1, ffi.cast('const int*', idx.ptr),
                                mats and mats.ptr or nil, gains and gains.ptr or nil, n, s, cs, fine and fine.ptr or nil,
@@ -975,7 +1000,7 @@ function M.photoDataset(photos, windowH, windowW, s, draw, fill)
     assert(photos:dim() == 4 and photos:size(1) >= 1, 'FG.photoDataset: [N][C][H][W] with N >= 1')
     assert(windowH >= 1 and windowW >= 1 and s >= 1, 'FG.photoDataset: positive sizes')
     assert(draw == nil or type(draw) == 'function', 'FG.photoDataset: draw(n, hs, ws) -> mats, gains')
-    return setmetatable({photos = dev, n = photos:size(1), c = photos:size(2),
+    return setmetatable({photos = dev, n = photos:size(1), c = storage == 'u8y' and 1 or photos:size(2), setC = photos:size(2),
                          photoH = photos:size(3), photoW = photos:size(4), windowH = windowH, windowW = windowW, h = s, w = s, draw = draw,
                          fill = fill or 0, storage = storage}, Photos)
 end
@@ -1008,7 +1033,11 @@ function Photos:gatherFields(picks, fields, cs, n, outLayout, augment)
     end
     local mats, gains
     if self.draw and augment ~= false then mats, gains = self.draw(n, self.photoH, self.photoW) else mats = self:identity(n) end
-    if self.storage == 'u8' then
+    if self.storage == 'u8y' then
+        check(C.fg_warp_faces_u8_y(ctx, self.photos.bytes, self.n, self.photoH, self.photoW, 1, ffi.cast('const int*', idx.ptr), mats.ptr,
+                                   gains and gains.ptr or nil, n, self.windowH, self.windowW, s, cs, out.fine and out.fine.ptr or nil,
+                                   out.coarse and out.coarse.ptr or nil, out.diff and out.diff.ptr or nil, self.fill))
+    elseif self.storage == 'u8' then
         check(C.fg_warp_faces_u8(ctx, self.photos.bytes, self.n, self.c, self.photoH, self.photoW, 1, ffi.cast('const int*', idx.ptr), mats.ptr,
                                  gains and gains.ptr or nil, n, self.windowH, self.windowW, s, cs, out.fine and out.fine.ptr or nil,
                                  out.coarse and out.coarse.ptr or nil, out.diff and out.diff.ptr or nil, outLayout or 0, self.fill))
