@@ -506,7 +506,9 @@ __device__ __forceinline__ float fg_prep_grad(float g, float p, float gscale, fl
         const float a = fg_sgnf(p) * l1mul, b = p * l2;
         g = g + (a + b);
     }
-    if (clamp != 0.f) g = fminf(fmaxf(g, -clamp), clamp);             // adversarial.lua:121-123
+    // adversarial.lua:121-123: TH's clamp is compare-and-select, so a NaN gradient stays NaN (fminf / fmaxf would return the bound)
+    // and +-inf becomes +-clamp; a finite gradient keeps its bits
+    if (clamp != 0.f) g = (g < -clamp) ? -clamp : ((g > clamp) ? clamp : g);
     return g;
 }
 struct AdamScalars { float step, ob1, ob2; };      // lr * sqrt(1 - b2^t) / (1 - b1^t), 1 - b1, 1 - b2 (host side, in double)

@@ -104,7 +104,9 @@ __device__ __forceinline__ void fg_epilogue(const IgemmArgs& a, float* outp, con
                     const int vo = colok ? (int)(((unsigned)ro[i] + (unsigned)col) * 4u) : FG_OOB;   // unsigned: a masked row wraps past 2 GiB
                     const float g = acc[mi][ni][i];
                     const bool pos = xv[i] > 0.f;
-                    t4[i & 3] = fmaf(pos ? 0.f : xv[i], g, t4[i & 3]);   // masked elements read x = 0: they add 0 * g
+                    // a select, as prelu_bwd_kernel skips: 0 * inf would be NaN.  A column past N is skipped as well: its accumulator is
+                    // gy times zero-filled weights, NaN in a row whose gy holds an inf (a masked row read x = 0 and g = 0: it adds 0)
+                    t4[i & 3] = (pos || !colok) ? t4[i & 3] : fmaf(xv[i], g, t4[i & 3]);
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pos ? g : sl * g), orsrc, vo, 0, 0);
                 }
                 s += (t4[0] + t4[1]) + (t4[2] + t4[3]);

@@ -1355,7 +1355,17 @@ int fg_launch_leakyrelu_backward(fg_ctx* ctx, const float* x, const float* gy, f
 }
 
 // ------------------------------------------------------------------ SpatialMaxPooling(2,2) (models_c2f.lua:251, 256)
-// ties: first max in scan order (dy, dx); backward recomputes the argmax from the saved input (no index tensor)
+// backward recomputes the argmax from the saved input (no index tensor).  ONE scan decides the slot for all four max-pool kernels:
+// the window's first NaN wins if it holds one, otherwise the first maximum in scan order (dy, dx) -- a tie, -0 against +0 included,
+// stays with the earlier slot.  m = that slot's value, bit for bit (a copy, no arithmetic).
+__device__ __forceinline__ int fg_maxscan4(float v0, float v1, float v2, float v3, float& m) {
+    int am = 0;
+    m = v0;
+    if (m == m && (v1 > m || v1 != v1)) { m = v1; am = 1; }
+    if (m == m && (v2 > m || v2 != v2)) { m = v2; am = 2; }
+    if (m == m && (v3 > m || v3 != v3)) { m = v3; am = 3; }
+    return am;
+}
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H,
                                                           int W, int C) {
     const int H2 = H >> 1, W2 = W >> 1, C4 = C >> 2;
@@ -1365,10 +1375,10 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
         int c4, w2, h2, b;
         fg_decode_quad(i, C4, W2, H2, c4, w2, h2, b);
         const float4* px = (const float4*)(x + (((size_t)b * H + 2 * h2) * W + 2 * w2) * C) + c4;
-        float4 m = px[0];
-        const float4 v1 = px[C4], v2 = px[(size_t)W * C4], v3 = px[(size_t)W * C4 + C4];
-        m.x = fmaxf(fmaxf(m.x, v1.x), fmaxf(v2.x, v3.x)); m.y = fmaxf(fmaxf(m.y, v1.y), fmaxf(v2.y, v3.y));
-        m.z = fmaxf(fmaxf(m.z, v1.z), fmaxf(v2.z, v3.z)); m.w = fmaxf(fmaxf(m.w, v1.w), fmaxf(v2.w, v3.w));
+        const float4 v0 = px[0], v1 = px[C4], v2 = px[(size_t)W * C4], v3 = px[(size_t)W * C4 + C4];
+        float4 m;
+        fg_maxscan4(v0.x, v1.x, v2.x, v3.x, m.x); fg_maxscan4(v0.y, v1.y, v2.y, v3.y, m.y);
+        fg_maxscan4(v0.z, v1.z, v2.z, v3.z, m.z); fg_maxscan4(v0.w, v1.w, v2.w, v3.w, m.w);
         ((float4*)y)[i] = m;
     }
 }
@@ -1385,10 +1395,8 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
         const int b = (int)(t / H2);
         const size_t base = (((size_t)b * H + 2 * h2) * W + 2 * w2) * C + c;
         const size_t o[4] = {base, base + C, base + (size_t)W * C, base + (size_t)W * C + C};
-        int am = 0;
-        float m = x[o[0]];
-#pragma unroll
-        for (int k = 1; k < 4; ++k) { const float v = x[o[k]]; if (v > m) { m = v; am = k; } }
+        float m;
+        const int am = fg_maxscan4(x[o[0]], x[o[1]], x[o[2]], x[o[3]], m);
         const float g = gy[i];
 #pragma unroll
         for (int k = 0; k < 4; ++k) gx[o[k]] = (k == am) ? g : 0.f;
@@ -1418,10 +1426,9 @@ __global__ __launch_bounds__(256) void maxpool_prelu_bwd_kernel(const float* __r
         float xv[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) xv[k] = xpre[o[k]];
-        int am = 0;
-        float m = xv[0] > 0.f ? xv[0] : a * xv[0];
-#pragma unroll
-        for (int k = 1; k < 4; ++k) { const float v = xv[k] > 0.f ? xv[k] : a * xv[k]; if (v > m) { m = v; am = k; } }
+        auto act = [a](float v) { return v > 0.f ? v : a * v; };
+        float m;
+        const int am = fg_maxscan4(act(xv[0]), act(xv[1]), act(xv[2]), act(xv[3]), m);
         const float g = mask ? gy[i] * (mask[i] * mscale) : gy[i];           // mul_mask_kernel's expression
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -1468,10 +1475,10 @@ __global__ __launch_bounds__(256) void actmaxpool_fwd_kernel(const float* __rest
         const float4 v0 = px[0], v1 = px[C4], v2 = px[(size_t)W * C4], v3 = px[(size_t)W * C4 + C4];
         auto act = [a](float v) { return v > 0.f ? v : a * v; };
         float4 m;
-        m.x = fmaxf(fmaxf(act(v0.x), act(v1.x)), fmaxf(act(v2.x), act(v3.x)));
-        m.y = fmaxf(fmaxf(act(v0.y), act(v1.y)), fmaxf(act(v2.y), act(v3.y)));
-        m.z = fmaxf(fmaxf(act(v0.z), act(v1.z)), fmaxf(act(v2.z), act(v3.z)));
-        m.w = fmaxf(fmaxf(act(v0.w), act(v1.w)), fmaxf(act(v2.w), act(v3.w)));
+        fg_maxscan4(act(v0.x), act(v1.x), act(v2.x), act(v3.x), m.x);
+        fg_maxscan4(act(v0.y), act(v1.y), act(v2.y), act(v3.y), m.y);
+        fg_maxscan4(act(v0.z), act(v1.z), act(v2.z), act(v3.z), m.z);
+        fg_maxscan4(act(v0.w), act(v1.w), act(v2.w), act(v3.w), m.w);
         if (mask) {
             const float4 k = ((const float4*)mask)[i];
             m.x = m.x * (k.x * mscale); m.y = m.y * (k.y * mscale); m.z = m.z * (k.z * mscale); m.w = m.w * (k.w * mscale);
@@ -1863,7 +1870,7 @@ __global__ __launch_bounds__(256) void gemv_bwd_act_kernel(const float* __restri
                 if (mask) g = g * (mask[i] * mscale);
                 const float xv = xp[i];
                 const bool pos = xv > 0.f;
-                ss = fmaf(pos ? 0.f : xv, g, ss);
+                ss = pos ? ss : fmaf(xv, g, ss);            // a select, as prelu_bwd_kernel skips: 0 * inf would be NaN
                 g = pos ? g : sl * g;
             }
             gx[i] = g;

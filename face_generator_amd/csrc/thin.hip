@@ -38,8 +38,8 @@ template <int EPI>
 __device__ __forceinline__ void thin_epi_store(const ThinEpi& e, float sl, float* __restrict__ out, size_t idx, float v0, float v1,
                                                float x0, float x1, float& s) {
     if constexpr (EPI == 2) {          // x0 / x1: the PReLU input at idx / idx + 32, fetched before the tile's MFMA loop
-        s = fmaf(x0 > 0.f ? 0.f : x0, v0, s);
-        s = fmaf(x1 > 0.f ? 0.f : x1, v1, s);
+        s = x0 > 0.f ? s : fmaf(x0, v0, s);          // (a select, as prelu_bwd_kernel skips: 0 * inf would be NaN)
+        s = x1 > 0.f ? s : fmaf(x1, v1, s);
         out[idx] = x0 > 0.f ? v0 : sl * v0;
         out[idx + 32] = x1 > 0.f ? v1 : sl * v1;
     } else {
@@ -382,8 +382,8 @@ __global__ __launch_bounds__(256) void thin_in_mfma_pad_kernel(const float* __re
             const float v0 = acc0[r], v1 = acc1[r];
             if constexpr (EPI == 2) {
                 const float x0 = px0[r], x1 = px1[r];
-                es = fmaf(x0 > 0.f ? 0.f : x0, v0, es);                 // (an element past the end read x = 0 and v is finite)
-                es = fmaf(x1 > 0.f ? 0.f : x1, v1, es);
+                es = x0 > 0.f ? es : fmaf(x0, v0, es);                  // (an element past the end read x = 0 and v is finite)
+                es = x1 > 0.f ? es : fmaf(x1, v1, es);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x0 > 0.f ? v0 : esl * v0), ors, vo, so, 0);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x1 > 0.f ? v1 : esl * v1), ors, vo + 128, so, 0);
             } else {

@@ -153,6 +153,10 @@ int fg_nchw_to_nhwc(fg_ctx* ctx, const float* src, float* dst, int n, int c, int
 int fg_nhwc_to_nchw(fg_ctx* ctx, const float* src, float* dst, int n, int c, int h, int w);
 
 /* ---- RNG: torch.Tensor:uniform / :bernoulli / randn (nn_utils.lua:9, 37; nn.Dropout) -- Philox4x32-10 ---- */
+/* Values (tests/POINTWISE_DOMAIN.md): u = (word >> 8) * 2^-24 lies in [0, 1 - 2^-24].  fg_rng_uniform = lo + u * (hi - lo) in fp32: lo
+ * occurs, and hi ITSELF occurs wherever lo + (1 - 2^-24) (hi - lo) rounds up to it -- (0.5, 1.5) yields 1.5; (0, 1) does not yield
+ * 1, and (-1, 1), the noise range of nn_utils.lua:9, does not yield 1 (its largest value is 1 - 2^-23).  fg_rng_bernoulli = u <
+ * keep_prob: keep 0 gives all 0, keep 1 all 1.  fg_rng_normal takes u1 = ((word >> 8) + 1) * 2^-24 in (0, 1]: always finite. */
 int fg_rng_uniform(fg_ctx* ctx, uint64_t seed, uint64_t offset, float* out, long long n, float lo, float hi);
 int fg_rng_bernoulli(fg_ctx* ctx, uint64_t seed, uint64_t offset, float* out, long long n, float keep_prob);
 int fg_rng_normal(fg_ctx* ctx, uint64_t seed, uint64_t offset, float* out, long long n, float mean, float std);
@@ -308,7 +312,11 @@ int fg_bce_forward_backward(fg_ctx* ctx, const float* prob, const float* target,
  *      adversarial.lua:103-123 / 218-228 fused in:  g' = clamp(gscale*g + l1_mul*sign(p) + l2*p, +-clamp).
  *      Hyper-parameters are doubles (Lua numbers): 1-beta, the bias corrections and the step size are evaluated in
  *      double on the host exactly like interruptable_optimizers.lua:78-88, then rounded to fp32 once.
- *      Alignment: every vector (p, g, m, v, mom_buf, variance, g_out) needs 4 bytes only, at any n >= 0. ---- */
+ *      Alignment: every vector (p, g, m, v, mom_buf, variance, g_out) needs 4 bytes only, at any n >= 0.
+ *      Non-finite gradients: the clamp is compare-and-select, as TH's clamp and numpy's clip are.  A NaN gradient stays NaN with
+ *      the clamp on or off -- the parameter, the optimizer state and g_out of that element become NaN, under all three rules and
+ *      in the fused Adam + re-pack launch of the step level -- and +-inf under a clamp becomes +-clamp.  A finite gradient keeps
+ *      its bits.  (A NaN PARAMETER reaches g' only through the penalty term.) ---- */
 int fg_adam_fused(fg_ctx* ctx, float* p, const float* g, float* m, float* v, long long n, float gscale, float l1_mul,
                   float l2, float clamp, double lr, double beta1, double beta2, double eps, int t, float* g_out);
 int fg_sgd_fused(fg_ctx* ctx, float* p, const float* g, float* mom_buf, long long n, float gscale, float l1_mul,
@@ -316,7 +324,10 @@ int fg_sgd_fused(fg_ctx* ctx, float* p, const float* g, float* mom_buf, long lon
                  int first_step);
 int fg_adagrad_fused(fg_ctx* ctx, float* p, const float* g, float* variance, long long n, float gscale, float l1_mul,
                      float l2, float clamp, double clr);
-/* out2[0] = ||p||_1, out2[1] = ||p||_2^2 (torch.norm of adversarial.lua:105-106); scratch >= 1024 floats */
+/* out2[0] = ||p||_1, out2[1] = ||p||_2^2 (torch.norm of adversarial.lua:105-106); scratch >= 1024 floats.  The squares and their
+ * partial sums are fp32 (the final sum of the partials is double, stored as fp32): out2[1] is +inf as soon as a square or a block's
+ * sum exceeds FLT_MAX -- from |p_i| ~ 1.8e19 on, although ||p||_2 itself is representable -- and squares below 2^-149 count as 0.
+ * A NaN element makes both results NaN; an infinite one makes both +inf. */
 int fg_norms(fg_ctx* ctx, const float* p, long long n, float* out2_dev, float* scratch);
 
 /* ---- data parallelism: one process (rank) per GPU, RCCL over xGMI (SURVEY.md 8(b) `fg_allreduce_sum(fg_comm*, ...)`, 8(e)).
@@ -458,6 +469,10 @@ int fg_test_set_gan_bucket_target(fg_gan* gan, long long floats);
  *   every element no image covers holds the maximum over the k selected images.  normalize = 1 maps the whole grid by
  *   (v - min) / (max - min), min / max over the k selected images (max == min: all 0); normalize = 0 keeps raw values.
  *   minmax_out: device float[2] = {min, max}, or NULL.  The reduction runs in a fixed order.
+ *   Non-finite pixels: min and max are fmin / fmax reductions, which skip a NaN, so a NaN pixel stays NaN in the grid and changes
+ *   no other element (all pixels NaN: min = +inf, max = -inf).  An infinite pixel IS an extremum: with normalize = 1 and max = +inf
+ *   every finite pixel maps to 0 and the pixel itself and the padding (which holds the maximum) to NaN; min = -inf maps every
+ *   finite pixel to NaN.
  *
  * fg_sampler: G and D are fg_net objects bound to their vectors; neither may be a table-input net (the c2f pair of fg_gan's
  *   table_inputs = 1 is refused, FG_ERR_UNSUPPORTED).  D may be any net that compiles to one plan, nn.ConcatTable ones included.
@@ -829,7 +844,10 @@ int fg_batchnorm_backward(fg_ctx* ctx, const float* x, const float* gy, float* g
                           const float* gamma, const float* beta, const float* slope, const float* save_mean,
                           const float* save_invstd, float* ggamma, float* gbeta, float* gslope, float acc,
                           float* scratch);
-/* PReLU with an optional same-shape keep mask (x mscale): nn.PReLU [+ nn.Dropout]; scratch >= 1024 floats */
+/* PReLU with an optional same-shape keep mask (x mscale): nn.PReLU [+ nn.Dropout]; scratch >= 1024 floats.  gslope sums x * g over
+ * the units with !(x > 0) and SKIPS the others: a non-finite gradient at a positive input does not reach it.  The forms fused into
+ * the thin-layer, implicit-GEMM (single-pass and split-K) and Linear(-> 1) data gradients of fg_net do the same (the Winograd epilogue multiplies by a selected
+ * zero instead; a non-finite gradient is already NaN across its tile there). */
 int fg_prelu_forward(fg_ctx* ctx, const float* x, const float* slope, const float* mask, float mscale, float* y,
                      long long n);
 int fg_prelu_backward(fg_ctx* ctx, const float* x, const float* gy, const float* slope, const float* mask,
@@ -852,8 +870,12 @@ int fg_upsample_nearest2x_backward(fg_ctx* ctx, const float* gy, float* gx, int 
  * forward: conv output -> viewed output; backward: gradient wrt the viewed output -> gradient wrt the conv output. */
 int fg_conv_upsample_view_forward(fg_ctx* ctx, const float* conv_out, float* viewed, int batch, int h, int w, int c, int factor);
 int fg_conv_upsample_view_backward(fg_ctx* ctx, const float* g_viewed, float* g_conv_out, int batch, int h, int w, int c, int factor);
-/* nn.SpatialMaxPooling(2,2): backward recomputes the argmax (first max in scan order) from the saved input.  h and w even, and
- * for the forward pass c % 4 == 0 (FG_ERR_INVALID otherwise, nothing is launched) */
+/* nn.SpatialMaxPooling(2,2): backward recomputes the argmax from the saved input.  h and w even, and for the forward pass c % 4 == 0
+ * (FG_ERR_INVALID otherwise, nothing is launched).  The slot of a window, for the forward and the backward pass and for the fused
+ * PReLU + max-pool stages of fg_net alike (one shared scan): the window's first NaN in scan order (dy, dx) if it holds one,
+ * otherwise its first maximum; a tie stays with the earlier slot, -0 against +0 included.  The forward value is that slot's bits
+ * (behind a fused PReLU: of slope * x, so a NaN's payload need not survive); the backward pass writes gy to that slot and +0 to
+ * the other three. */
 int fg_maxpool2x2_forward(fg_ctx* ctx, const float* x, float* y, int batch, int h, int w, int c);
 int fg_maxpool2x2_backward(fg_ctx* ctx, const float* x, const float* gy, float* gx, int batch, int h, int w, int c);
 /* nn.Dropout on any shape: y = x * mask * scale (mask NULL: y = x * scale) */
@@ -871,6 +893,8 @@ int fg_split_rows(fg_ctx* ctx, const float* g, float* const* parts, const int* w
 int fg_sum_n(fg_ctx* ctx, const float* const* parts, int n, float* out, long long count);
 int fg_sigmoid_forward(fg_ctx* ctx, const float* x, float* y, long long n);
 int fg_sigmoid_backward(fg_ctx* ctx, const float* y, const float* gy, float* gx, long long n);
+/* LeakyReLU.lua:13-31's own formula, y = (|x| + x) / 2 + (|x| - x) * (-negslope / 2): as in the reference, x = +inf gives NaN
+ * (inf - inf; -inf as well) and x > FLT_MAX / 2 gives +inf.  backward: x >= 0 ? gy : negslope * gy (a NaN x takes the second). */
 int fg_leakyrelu_forward(fg_ctx* ctx, const float* x, float negslope, float* y, long long n);
 int fg_leakyrelu_backward(fg_ctx* ctx, const float* x, const float* gy, float negslope, float* gx, long long n);
 

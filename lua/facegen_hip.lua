@@ -540,6 +540,8 @@ end
 
 -- interruptable_optimizers.lua on DEVICE vectors (x, dfdx = DeviceTensor); `fused` carries penalty / clamp / 1/world.
 -- `net` (a DeviceNet) is told that its parameters moved: the packed / tap-folded weights are rebuilt before its next use.
+-- The clamp is compare-and-select like GRAD_PARAMETERS:clamp(..): a NaN gradient stays NaN (parameter and state become NaN, clamp
+-- on or off), +-inf becomes +-clamp.
 local function fused_args(fused) fused = fused or {}; return fused.gscale or 1, fused.l1_mul or 0, fused.l2 or 0, fused.clamp or 0 end
 function M.interruptableAdam(opfunc, x, config, state, fused, net)
     config = config or {}; state = state or config
